@@ -12,6 +12,7 @@ fp16 activations) and the caches are resident in HBM before the timed region.
 The model's linear layers are NOT part of this path.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--ctx 131072] [--bits 4] [--sinks 0]
+  python bench.py ... --dump-outputs DIR   # also write the last timed step's attention outputs as DIR/attn_out.npy
   python bench.py --sweep          # one JSON line per BASELINE configuration (4K hot/rotated, 32K, 128K, 1M;
                                    # nuq4 and nuq3 + 5 sinks), the default line last
 
@@ -79,6 +80,10 @@ def parse():
     ap.add_argument("--no-full-model", action="store_true",
                     help="skip the full-model leg (random-init LLaMA-2-7B-shaped fp16 weights over the same filled caches)")
     ap.add_argument("--cpu-sample-tokens", type=int, default=8192)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller -- every layer's attention "
+                         "output, f32 [streams, layers, H, hd] -- as DIR/attn_out.npy (DIR/attn_out_rank<r>.npy per rank "
+                         "when N > 1); the inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args()
 
 
@@ -787,6 +792,16 @@ def check_memory(args, n_layers, streams, max_len, dev, what):
     return need
 
 
+def dump_outputs(out_dir, name, outs):
+    """outs: [stream][layer] f32 [1, H, hd] tensors -> out_dir/name.npy, f32 [streams, layers, H, hd]"""
+    import numpy as np
+    a = torch.stack([torch.stack(row) for row in outs]).reshape(len(outs), len(outs[0]), H, HD).cpu().numpy()
+    if a.nbytes > 64 << 20:
+        raise SystemExit("--dump-outputs: %s would be %.0f MB (at most 64 MB)" % (name, a.nbytes / 2 ** 20))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
 def run_config(args, rank, world, dev, dist, label=None, with_baselines=True):
     """build the caches of one configuration, time args.steps decode steps, return the result dict (rank 0) or None"""
     from kvquant_amd import sharding
@@ -823,12 +838,19 @@ def run_config(args, rank, world, dev, dist, label=None, with_baselines=True):
     torch.cuda.synchronize()
     t_setup = time.time() - t_setup
 
+    # --dump-outputs: the headline's last timed step keeps a reference to every layer's output (decode_kv allocates
+    # a fresh one per call, so this adds no launch to the timed region)
+    last_step = args.warmup + args.steps - 1 if (getattr(args, "dump_outputs", None) and label is None) else None
+    last_outs = {}
+
     def stage(s, step, x):
         for li in owned:
             q = qs[(s, li)][step]
             if sharded and li == owned[0]:
                 q = q + x.view(H, HD) * 1e-3          # the hand-over is a true data dependency of this stage
             out = layer_step(caches[(s, li)], q, ks[(s, li)][step], vs[(s, li)][step])
+            if step == last_step:
+                last_outs[(s, li)] = out
         return out.half().view(1, 1, C)
 
     template = torch.zeros(1, 1, C, dtype=torch.float16, device=dev)
@@ -854,6 +876,9 @@ def run_config(args, rank, world, dev, dist, label=None, with_baselines=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     timers.uninstall()
+    if last_step is not None:
+        dump_outputs(args.dump_outputs, "attn_out" if world == 1 else "attn_out_rank%d" % rank,
+                     [[last_outs[(s, li)] for li in owned] for s in range(streams)])
     retrieval = None
     if args.retrieval and plant_q is not None:
         retrieval = check_retrieval(caches[(0, owned[0])], rope_rotate(plant_q, args.ctx + args.sinks + total).half(), dev)
@@ -1019,6 +1044,9 @@ def other_configs(args, rank, world, dev, dist):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.prefill or args.shard != "layers"):
+        raise SystemExit("--dump-outputs writes the decode step of the layer placement (not --prefill / --shard %s)"
+                         % args.shard)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product path has no CPU fallback)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -90,3 +90,21 @@ def test_bench_prefill_line_contract():
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert abs(r["achieved"] - r["algorithmic_bytes_per_launch"] / (r["avg_launch_us"] * 1e-6) / 1e9) < 1e-6 * r["achieved"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's per-layer attention outputs, f32 [streams, layers, H, hd], from inputs that
+    are the same on every run with the same arguments"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    outs = []
+    for i in range(2):
+        d = _run("--ctx", "2048", "--layers", "2", "--steps", "3", "--warmup", "1", "--no-configs", "--no-cpu-baseline",
+                 "--no-fp16-baseline", "--no-full-model", "--dump-outputs", str(tmp_path / str(i)))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / str(i))) == ["attn_out.npy"]
+        outs.append(np.load(tmp_path / str(i) / "attn_out.npy"))
+    a, b = outs
+    assert a.dtype == np.float32 and a.shape == (1, 2, 32, 128) and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.abs(a - b).max() <= 1e-5 * np.abs(a).max(), np.abs(a - b).max()

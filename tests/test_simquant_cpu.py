@@ -1,6 +1,6 @@
 """oracle/simquant.py (restatement of the reference's simulated-quantisation functions) against the reference:
-bit-exact vs tests/golden/simquant_ref.npz (made by the reference's own module, tests/golden/gen_simquant.py)
-and, where /root/reference exists, vs that module imported live."""
+bit-exact vs tests/golden/simquant_ref.npz and tests/golden/simquant_wrappers_ref.npz (made by the reference's own
+module, tests/golden/gen_simquant.py)."""
 import os
 
 import numpy as np
@@ -33,23 +33,18 @@ def test_simquant_matches_reference_golden(bits):
         assert np.array_equal(t.numpy(), ref), name
 
 
-@pytest.mark.skipif(not os.path.exists(gen.REF), reason="no /root/reference here")
 def test_simquant_matches_reference_live():
-    ref = gen.load_ref()
-    k, v, up, lo, lut = gen.inputs(4, T=40, C=512, seed=7)
-    mk = ref.get_outliers(k, channel=0, outlier_threshold_upper=up, outlier_threshold_lower=lo, cap_outliers=21, first_few_fp16=3)
-    assert torch.equal(mk, sq.get_outliers(k, channel=0, outlier_threshold_upper=up, outlier_threshold_lower=lo, cap_outliers=21,
-                                           first_few_fp16=3))
-    a = ref.quant_fn_nuq_recon(k, bits=4, qchannel=0, maxval=up, minval=lo, include_sparse=True, outlier_mask=mk, lut=lut,
-                               first_few_fp16=3)
+    """first-token exclusion and the QuantLinearSim.forward argument plumbing (SQ:700-795) on a longer input, vs the
+    reference's outputs stored in tests/golden/simquant_wrappers_ref.npz"""
+    g = np.load(gen.WRAPPERS)
+    k, v, up, lo, lut = gen.wrapper_inputs()
+    mk = sq.get_outliers(k, channel=0, outlier_threshold_upper=up, outlier_threshold_lower=lo, cap_outliers=21,
+                         first_few_fp16=3)
+    assert np.array_equal(mk.numpy(), g["mk3"])
     b = sq.quant_fn_nuq_recon(k, bits=4, qchannel=0, maxval=up, minval=lo, include_sparse=True, outlier_mask=mk, lut=lut,
                               first_few_fp16=3)
-    assert torch.equal(a, b)
+    assert np.array_equal(b.numpy(), g["q3"])
     quant = (up.float().numpy()[None], lo.float().numpy()[None], lut)
     # the wrappers reproduce QuantLinearSim.forward's argument plumbing (SQ:700-795)
-    mk0 = ref.get_outliers(k, channel=0, outlier_threshold_upper=up, outlier_threshold_lower=lo, cap_outliers=21)
-    a0 = ref.quant_fn_nuq_recon(k, bits=4, qchannel=0, maxval=up, minval=lo, include_sparse=True, outlier_mask=mk0, lut=lut)
-    assert torch.equal(sq.fake_quant_k(k, quant, 4, cap_outliers=21), a0.half())
-    mv = ref.get_outliers_dynamic(v, channel=-1, thresh=0.99)
-    c = ref.quant_fn_nuq_recon(v, bits=4, qchannel=-1, include_sparse=True, outlier_mask=mv, dynamicquantization=True, lut=lut)
-    assert torch.equal(sq.fake_quant_v(v, quant, 4, sparsity_threshold=0.99), c.half())
+    assert torch.equal(sq.fake_quant_k(k, quant, 4, cap_outliers=21), torch.from_numpy(g["qk"]).half())
+    assert torch.equal(sq.fake_quant_v(v, quant, 4, sparsity_threshold=0.99), torch.from_numpy(g["qv"]).half())
