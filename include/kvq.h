@@ -70,6 +70,9 @@ extern "C" {
  *   402  round 6: new entries kvq_score_k_mirror, kvq_outlier_mirror_rows (the mirror variant of q.K^T for callers that
  *        keep the reference's outlier rows); new flag values KVQ_SCORE_F32_PAIR_TABLES / KVQ_LAYER_SCORE_F32_PAIR;
  *        kvq_score_k_workspace_bytes is 16 KB per head larger at 3 bit.
+ *   403  grouped-query attention (GQA): new entries kvq_gqa_supported, kvq_score_k_gqa[_workspace_bytes, _parts],
+ *        kvq_mix_v_gqa[_workspace_bytes], kvq_decode_step_gqa[_workspace_bytes], kvq_prefill_attention_gqa.  Every
+ *        existing entry point, struct and behaviour is unchanged.
  *        A binding checks `kvq_version() / 100 == KVQ_ABI_MAJOR`. */
 #define KVQ_ABI_MAJOR 4
 KVQ_API int kvq_version(void);
@@ -530,6 +533,60 @@ KVQ_API int kvq_prefill_attention(const void *q, const void *k, const void *v, v
                           int64_t q_stride_h, int64_t q_stride_s, int64_t k_stride_h, int64_t k_stride_s,
                           int64_t v_stride_h, int64_t v_stride_s, int64_t o_stride_h, int64_t o_stride_s,
                           float softmax_scale, void *stream);
+
+/* ---- grouped-query attention (GQA, ABI 403) ------------------------------------------------------------------------
+ * Hq query heads share Hkv KV heads, G = Hq / Hkv query heads per KV head; query head h attends to KV head h / G
+ * (transformers' repeat_kv).  The caches are the ordinary ones with H = Hkv (`mat` [Hkv][hd/32*bits][max_len], K look-up
+ * table [Hkv][hd][2^bits], outlier channels global over Hkv*hd).  Supported: 1 <= G <= 8, Hkv*hd <= 8192, hd = 128;
+ * every violation is KVQ_EINVAL before any launch.  With G = 1 the results are those of the MHA entries (sums in another
+ * order).  kvq_gqa_supported: 1 if (Hq, Hkv, hd) is such a shape, else 0. */
+KVQ_API int kvq_gqa_supported(int Hq, int Hkv, int hd);
+/* q.K^T, one pass over each KV head's packed K:
+ *   mul[h][t] = sum_k Khat[h/G][k][t] * (cos(a)*q[h][k] + sgn_k*sin(a)*q[h][(k+64)%128]),  h < Hq, t < L,
+ * with the angle, position and sign rules of kvq_score_k and Khat = lut[h/G][k][code] + the token's K outlier entries of
+ * KV head h/G from the token-contiguous mirror outliers_t / outlier_idx_t [n_out][max_len] (both NULL: dense only; the
+ * compact format is not taken).  q: [Hq][128], fp32 (q_is_half = 0) or fp16 (1).  mul: f32 [Hq][L] (overwritten).
+ * softmax_parts (optional): f32 [Hq][n_parts][2], n_parts = kvq_score_k_gqa_parts(L), per query head and 64-token part
+ * (max, sum of exp) of the scaled scores half(half(mul) * inv_sqrt_hd) -- the partials kvq_softmax_finish takes over the
+ * Hq rows.  workspace: kvq_score_k_gqa_workspace_bytes(bits, Hq, Hkv) bytes, 16-byte aligned. */
+KVQ_API size_t kvq_score_k_gqa_workspace_bytes(int bits, int Hq, int Hkv);
+KVQ_API int kvq_score_k_gqa_parts(int64_t L);
+KVQ_API int kvq_score_k_gqa(int bits, const void *q, int q_is_half, const int32_t *mat, float *mul, const float *lut,
+                            int Hq, int Hkv, int hd, int64_t L, int64_t max_len, float rope_theta, int pos_offset,
+                            const float *outliers_t, const int32_t *outlier_idx_t, int n_out, float inv_sqrt_hd,
+                            float *softmax_parts, int n_parts, void *workspace, size_t workspace_bytes, void *stream);
+/* p.V, one pass over each KV head's packed V:
+ *   mul[h][c] (+)= sum_t Vhat[h/G][c][t] * p[h][t],  h < Hq,
+ * Vhat = lut_rows[t][code] + the V outlier entries (reference rows [max_len][n_out], global channels; both NULL: dense
+ * only).  p: f32 [Hq][L]; mul: f32 [Hq][128]; accumulate != 0 adds into mul.  The outlier sums are exact (64-bit fixed
+ * point) and order independent, the token slabs are reduced in a fixed order: deterministic, no float atomics.
+ * workspace: kvq_mix_v_gqa_workspace_bytes(bits, Hq, Hkv, hd, L) bytes. */
+KVQ_API size_t kvq_mix_v_gqa_workspace_bytes(int bits, int Hq, int Hkv, int hd, int64_t L);
+KVQ_API int kvq_mix_v_gqa(int bits, const float *p, const int32_t *mat, float *mul, const float *lut_rows, int Hq, int Hkv,
+                          int hd, int64_t L, int64_t max_len, const float *outliers, const int32_t *outlier_idx, int n_out,
+                          int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+/* One decode token through one GQA layer, one call: kvq_append_kv_fused into column `col` of the layer's caches
+ * (layer->H = Hkv, the KV head count; k, v: [Hkv*hd]), kvq_score_k_gqa with the fused first softmax pass,
+ * kvq_softmax_finish over the Hq rows, kvq_mix_v_gqa:
+ *   out[h][c] = sum_t Vhat[h/G][c][t] * softmax_t(half(half(q[h] . Khat[h/G][:, t]) / sqrt(hd)))  over L = col + 1 tokens,
+ * probabilities rounded to fp16 as in kvq_decode_step.  q [Hq][128] (RoPE'd), k, v: all fp32 or all fp16
+ * (acts_are_half).  sink_scores (optional): fp16 [Hq][n_sink] already scaled scores of the fp16 sink tokens, which enter
+ * the softmax; sink_probs (out, fp16 [Hq][n_sink]) their probabilities.  v_sink (optional): fp16 [Hq][n_sink][128], then
+ * out also holds the sink tokens' share (as kvq_softmax_finish).  The layer must carry the K mirror and the reference
+ * outlier rows of V (layer->koutliers_t, kidx_t, voutliers, vidx).  out f32 [Hq][hd].  workspace:
+ * kvq_decode_step_gqa_workspace_bytes(bits, Hq, Hkv, hd, col + 1) bytes, 256-byte aligned.  kvq_decode_step_events
+ * records around the q.K^T and the p.V launches of this call too. */
+KVQ_API size_t kvq_decode_step_gqa_workspace_bytes(int bits, int Hq, int Hkv, int hd, int64_t L);
+KVQ_API int kvq_decode_step_gqa(const kvq_layer *layer, int Hq, int64_t col, const void *q, const void *k, const void *v,
+                                int acts_are_half, const uint16_t *sink_scores, int n_sink, const uint16_t *v_sink,
+                                uint16_t *sink_probs, float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* kvq_prefill_attention with Hq query heads over Hkv KV heads: q / out rows of head h, k / v rows of head h / G.
+ *   out[h][s][:] = softmax_j<=s(q[h][s].k[h/G][j] * softmax_scale) . v[h/G][j][:].
+ * Strides and alignment as kvq_prefill_attention; Hq % Hkv == 0, 1 <= G <= 8. */
+KVQ_API int kvq_prefill_attention_gqa(const void *q, const void *k, const void *v, void *out, int Hq, int Hkv, int S, int hd,
+                                      int64_t q_stride_h, int64_t q_stride_s, int64_t k_stride_h, int64_t k_stride_s,
+                                      int64_t v_stride_h, int64_t v_stride_s, int64_t o_stride_h, int64_t o_stride_s,
+                                      float softmax_scale, void *stream);
 
 /* ---- uncapped ("orig") Dense-and-Sparse variants, 4 bit only ------------------ */
 

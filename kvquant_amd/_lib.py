@@ -100,6 +100,17 @@ SIGNATURES = {
     "kvq_attend_step": (_i, [_ly, _i64, _vp, _i, _sk, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "kvq_head_shard_step": (_i, [_ly, _ly, _i, _i64, _vp, _vp, _vp, _i, _sk, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "kvq_prefill_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _vp]),
+    "kvq_gqa_supported": (_i, [_i, _i, _i]),
+    "kvq_score_k_gqa_workspace_bytes": (_sz, [_i, _i, _i]),
+    "kvq_score_k_gqa_parts": (_i, [_i64]),
+    "kvq_score_k_gqa": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _f, _i, _vp, _vp, _i, _f, _vp, _i, _vp, _sz,
+                             _vp]),
+    "kvq_mix_v_gqa_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
+    "kvq_mix_v_gqa": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "kvq_decode_step_gqa_workspace_bytes": (_sz, [_i, _i, _i, _i, _i64]),
+    "kvq_decode_step_gqa": (_i, [_ly, _i, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "kvq_prefill_attention_gqa": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
+                                       _f, _vp]),
     "kvq_append_k_sparse_orig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "kvq_append_v_sparse_orig": (_i, [_vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "kvq_spmv_k_rope_csr": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _f, _i, _vp]),

@@ -71,37 +71,61 @@ class RotaryDynamic(nn.Module):
         cls._last.clear()
 
 
+def gqa_groups(num_heads, num_key_value_heads=None):
+    """query heads per KV head of a layer with `num_heads` query heads and `num_key_value_heads` KV heads (None: MHA).
+    Grouped-query attention takes 1 <= G <= 8 with num_heads = G * num_key_value_heads; raises ValueError otherwise."""
+    if num_key_value_heads is None:
+        return 1
+    H, Hkv = int(num_heads), int(num_key_value_heads)
+    if Hkv <= 0 or H % Hkv:
+        raise ValueError("num_attention_heads = %d is not a multiple of num_key_value_heads = %d" % (H, Hkv))
+    if H // Hkv > 8:
+        raise ValueError("grouped-query attention with %d query heads per KV head: the kernels take at most 8" % (H // Hkv))
+    return H // Hkv
+
+
 class KVQuantAttention(nn.Module):
     fuse_sinks = True     # decode: the fp16 sink tokens' matmuls inside the decode launches (False: torch glue as in the reference)
 
     def __init__(self, hidden_size=4096, num_heads=32, abits=4, include_sparse=True, first_few_fp16=0,
                  maxseqlen=4096, rope_theta=10000.0, sparsity_threshold=0.99, device=None,
-                 dtype=torch.float16, bias=False, make_proj=True, use_orig_sparse=False, compact=False):
+                 dtype=torch.float16, bias=False, make_proj=True, use_orig_sparse=False, compact=False,
+                 num_key_value_heads=None):
         super().__init__()
         self.hidden_size = hidden_size
         self.num_heads = num_heads
         self.head_dim = hidden_size // num_heads
+        # grouped-query attention: num_key_value_heads KV heads, query head h reads KV head h // G (None: MHA)
+        self.num_key_value_heads = num_heads if num_key_value_heads is None else int(num_key_value_heads)
+        self.num_kv_groups = gqa_groups(num_heads, self.num_key_value_heads)
+        gqa = self.num_kv_groups > 1
+        if gqa and (compact or use_orig_sparse):
+            raise ValueError("grouped-query attention: the compact outlier format and the uncapped (orig) CSR variants "
+                             "are MHA only")
+        kv_hidden = self.num_key_value_heads * self.head_dim
+        if gqa and kv_hidden % 32:
+            raise ValueError("grouped-query attention: num_key_value_heads * head_dim must be a multiple of 32")
         self.first_few_fp16 = first_few_fp16
         self.rope_theta = rope_theta
         kw = dict(device=device, dtype=dtype)
         if make_proj:     # (kvquant_amd.llama wraps a model's own projections and only uses attend())
             self.q_proj = nn.Linear(hidden_size, hidden_size, bias=bias, **kw)
-            self.k_proj = nn.Linear(hidden_size, hidden_size, bias=bias, **kw)
-            self.v_proj = nn.Linear(hidden_size, hidden_size, bias=bias, **kw)
+            self.k_proj = nn.Linear(hidden_size, kv_hidden, bias=bias, **kw)
+            self.v_proj = nn.Linear(hidden_size, kv_hidden, bias=bias, **kw)
             self.o_proj = nn.Linear(hidden_size, hidden_size, bias=bias, **kw)
         self.rotary_emb = RotaryDynamic(self.head_dim, base=rope_theta, device=device)
-        self.kcache = QuantK(bits=abits, hidden_size=hidden_size, num_heads=num_heads,
+        self.kcache = QuantK(bits=abits, hidden_size=kv_hidden, num_heads=self.num_key_value_heads,
                              max_position_embeddings=maxseqlen, include_sparse=include_sparse,
                              sparsity_threshold=sparsity_threshold, rope_theta=rope_theta,
                              first_few_fp16=first_few_fp16, device=device, compact=compact)
-        self.vcache = QuantV(bits=abits, hidden_size=hidden_size, num_heads=num_heads,
+        self.vcache = QuantV(bits=abits, hidden_size=kv_hidden, num_heads=self.num_key_value_heads,
                              max_position_embeddings=maxseqlen, include_sparse=include_sparse,
                              sparsity_threshold=sparsity_threshold, first_few_fp16=first_few_fp16,
                              device=device, compact=compact)
         if first_few_fp16 > 0:
-            self.kcache_fp16 = torch.zeros((1, num_heads, self.head_dim, first_few_fp16), dtype=dtype,
+            self.kcache_fp16 = torch.zeros((1, self.num_key_value_heads, self.head_dim, first_few_fp16), dtype=dtype,
                                            device=self.kcache.device)
-            self.vcache_fp16 = torch.zeros((1, num_heads, first_few_fp16, self.head_dim), dtype=dtype,
+            self.vcache_fp16 = torch.zeros((1, self.num_key_value_heads, first_few_fp16, self.head_dim), dtype=dtype,
                                            device=self.kcache.device)
 
     def load_quantizers(self, k_quantizer, v_quantizer, include_sparse=True, sparsity_threshold=0.99, norm=False):
@@ -118,7 +142,10 @@ class KVQuantAttention(nn.Module):
     # ------------------------------------------------------------------ core (post-projection states)
     def attend(self, query_states, key_states, value_states):
         """query/key/value_states: [1, H, q_len, hd] (pre-RoPE), activation dtype.
-        Returns attn_output [1, q_len, hidden] (before o_proj)."""
+        Returns attn_output [1, q_len, hidden] (before o_proj).  Grouped-query attention: key / value_states carry
+        num_key_value_heads heads (attend_gqa)."""
+        if self.num_kv_groups > 1:
+            return self.attend_gqa(query_states, key_states, value_states)
         bsz, H, q_len, hd = query_states.shape
         assert bsz == 1, "batch 1 only (ML:1801)"
         sinks = self.first_few_fp16
@@ -202,11 +229,66 @@ class KVQuantAttention(nn.Module):
             out = out + torch.matmul(sink_probs.view(1, H, 1, sinks), self.vcache_fp16)
         return out.transpose(1, 2).contiguous().reshape(bsz, q_len, self.hidden_size)
 
+    def attend_gqa(self, query_states, key_states, value_states):
+        """attend() for grouped-query attention: query_states [1, Hq, q_len, hd], key / value_states [1, Hkv, q_len, hd]
+        (pre-RoPE).  Prefill: kvq_prefill_attention_gqa + the packs of the Hkv heads; decode: kvq_rope_q_f16 over the Hq
+        heads + one kvq_decode_step_gqa; the sink-filling phase in torch with the KV heads repeated per group."""
+        bsz, H, q_len, hd = query_states.shape
+        assert bsz == 1, "batch 1 only (ML:1801)"
+        G = self.num_kv_groups
+        sinks = self.first_few_fp16
+        key_states = key_states.half()
+        value_states = value_states.half()
+        start = self.kcache.klen
+        cos, sin = self.rotary_emb(value_states, start, start + q_len)
+        if not (self.kcache.include_sparse and self.vcache.include_sparse and hd == 128):
+            raise ValueError("grouped-query attention needs include_sparse caches and head_dim 128")
+        if q_len == 1 and start >= sinks:
+            if query_states.dtype != torch.float16 or (sinks > 0 and self.kcache_fp16.dtype != torch.float16):
+                raise ValueError("grouped-query attention decodes fp16 activations")
+            q_rope = ops.rope_q_f16(query_states.reshape(H, hd), cos[0], sin[0])
+            if sinks > 0:
+                out, _ = decode_kv(self.kcache, self.vcache, q_rope, key_states.flatten(), value_states.flatten(),
+                                   k_sink=self.kcache_fp16[0], v_sink=self.vcache_fp16[0])
+            else:
+                out, _ = decode_kv(self.kcache, self.vcache, q_rope, key_states.flatten(), value_states.flatten())
+            return out.half().view(bsz, q_len, self.hidden_size)
+        query_rope = (query_states * cos) + (rotate_half(query_states) * sin)
+        key_rope = (key_states * cos) + (rotate_half(key_states) * sin)
+        if q_len > 1 and self.kcache.klen == 0:
+            attn_output = ops.prefill_attention_gqa(query_rope[0].half(), key_rope[0], value_states[0]) \
+                .view(bsz, q_len, self.hidden_size).to(query_states.dtype)
+            if sinks > 0:
+                n = min(sinks, q_len)
+                self.kcache_fp16[:, :, :, :n] = key_rope[:, :, :n, :].transpose(2, 3)
+                self.vcache_fp16[:, :, :n, :] = value_states[:, :, :n, :]
+                if q_len > sinks:
+                    self.kcache.parallel_pack(key_states[0, :, sinks:, :].transpose(1, 2))
+                    self.vcache.parallel_pack(value_states[0, :, sinks:, :].transpose(1, 2))
+                self.kcache.klen += n
+                self.vcache.vlen += n
+            else:
+                self.kcache.parallel_pack(key_states[0].transpose(1, 2))
+                self.vcache.parallel_pack(value_states[0].transpose(1, 2))
+            return attn_output
+        assert q_len == 1, "decode feeds one token at a time (generation/utils.py kvquant hooks)"
+        # ---- still filling the fp16 sink caches (ML:1932-1946, 1981-1984), KV heads repeated per group
+        self.kcache_fp16[:, :, :, self.kcache.klen] = key_rope.transpose(2, 3).squeeze(-1)
+        self.kcache.klen += 1
+        ks = self.kcache_fp16[:, :, :, :self.kcache.klen].repeat_interleave(G, dim=1)
+        w = torch.matmul(query_rope, ks) / math.sqrt(hd)
+        w = F.softmax(w, dim=-1, dtype=torch.float32).to(query_rope.dtype)
+        self.vcache_fp16[:, :, self.vcache.vlen, :] = value_states.squeeze(2)
+        self.vcache.vlen += 1
+        out = torch.matmul(w, self.vcache_fp16[:, :, :self.vcache.vlen, :].repeat_interleave(G, dim=1))
+        return out.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
+
     def forward(self, hidden_states):
         """hidden_states [1, q_len, hidden] -> [1, q_len, hidden]."""
         bsz, q_len, _ = hidden_states.shape
         shape = (bsz, q_len, self.num_heads, self.head_dim)
+        kv_shape = (bsz, q_len, self.num_key_value_heads, self.head_dim)
         q = self.q_proj(hidden_states).view(shape).transpose(1, 2)
-        k = self.k_proj(hidden_states).view(shape).transpose(1, 2)
-        v = self.v_proj(hidden_states).view(shape).transpose(1, 2)
+        k = self.k_proj(hidden_states).view(kv_shape).transpose(1, 2)
+        v = self.v_proj(hidden_states).view(kv_shape).transpose(1, 2)
         return self.o_proj(self.attend(q, k, v))

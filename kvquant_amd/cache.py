@@ -17,6 +17,7 @@ work unchanged.  What changed underneath:
 There is no CPU fallback: the tensors live on a GPU and every op raises if the
 HIP library is missing.
 """
+import math
 import os
 import sys
 
@@ -595,7 +596,10 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     their scores are computed in the prologue launch and their share of the output in the softmax launch, so that
     `out` is the complete attention output (the reference's two fp16 matmuls, division and add: ML:1950-1962,
     1987-1995; five small launches per layer otherwise).
-    Returns (out f32 [1, H, hd], sink_probs f16 [H, n_sink] or None).  Sparse (include_sparse) caches only."""
+    Returns (out f32 [1, H, hd], sink_probs f16 [H, n_sink] or None).  Sparse (include_sparse) caches only.
+    Grouped-query attention: q of Hq = G * H rows (1 < G <= 8) over caches of H KV heads takes decode_kv_gqa."""
+    if q.dim() == 2 and q.shape[0] != kc.num_heads:
+        return decode_kv_gqa(kc, vc, q, k, v, sink_scores, k_sink, v_sink)
     if not (kc.include_sparse and vc.include_sparse):
         raise ValueError("decode_kv needs include_sparse caches")
     bits = kc.bits
@@ -658,6 +662,56 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     return out, sink_probs
 
 
+def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
+    """decode_kv for grouped-query attention: q [Hq, 128] RoPE'd, Hq = G * kc.num_heads (1 <= G <= 8); query head h
+    attends to KV head h // G (transformers' repeat_kv).  k, v: [Hkv*128] of the new token (all of q, k, v fp16 or all
+    fp32).  One library call (kvq_decode_step_gqa): append, grouped q.K^T (each packed word read once per KV head),
+    softmax over the Hq rows, grouped p.V.  sink_scores: optional f16 [Hq, n_sink] already scaled; or k_sink
+    (f16 [Hkv, 128, n_sink], post-RoPE) / v_sink (f16 [Hkv, n_sink, 128]), the fp16 sink caches of the KV heads: their
+    scores and values are repeated per group here (torch glue over the few sink tokens).
+    Returns (out f32 [1, Hq, hd], sink_probs f16 [Hq, n_sink] or None)."""
+    H = kc.num_heads
+    Hq = int(q.shape[0])
+    if Hq % H or not 1 <= Hq // H <= 8:
+        raise ValueError("decode_kv: q has %d heads, the caches %d KV heads -- grouped-query attention needs "
+                         "Hq = G * Hkv with 1 <= G <= 8" % (Hq, H))
+    if not (kc.include_sparse and vc.include_sparse):
+        raise ValueError("decode_kv (GQA) needs include_sparse caches")
+    if getattr(kc, "compact", False) or getattr(vc, "compact", False):
+        raise ValueError("decode_kv (GQA): the compact outlier format does not take grouped-query attention")
+    if FUSED_ATTEND:
+        raise ValueError("decode_kv (GQA): KVQ_FUSED_ATTEND (the fused split-L kernel) does not take grouped-query "
+                         "attention")
+    G = Hq // H
+    kpos = kc.klen - kc.first_few_fp16
+    vpos = vc.vlen - vc.first_few_fp16
+    if kpos != vpos:
+        raise ValueError("decode_kv (GQA): K and V caches must be in step")
+    lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
+    table = kc.lookup_table2 if (kc.norm and kc.bits == 2) else kc.lookup_table
+    inv = 1.0 / (kc.head_dim ** 0.5)
+    v_rep = None
+    if k_sink is not None:
+        if sink_scores is not None or v_sink is None:
+            raise ValueError("pass either sink_scores or (k_sink, v_sink)")
+        # the reference's fp16 matmul and division (ML:1950-1962) with the KV heads repeated per group
+        k_rep = k_sink.repeat_interleave(G, dim=0)
+        sink_scores = (torch.matmul(q.half().unsqueeze(1), k_rep) / math.sqrt(kc.head_dim))[:, 0, :].contiguous()
+        v_rep = v_sink.repeat_interleave(G, dim=0).contiguous()
+    key = (id(vc), getattr(vc, "_tables_version", 0), vc.reference_tie_quirk, vc.norm, kc.norm, kc.compact, vc.compact,
+           kc.score_f16_pair, getattr(kc, "score_f32_pair", False))
+    cached = getattr(kc, "_step_layer", None)
+    if cached is None or cached[0] != key:
+        cached = (key,) + ops.make_layer(kc, vc, table, lut_off)
+        kc._step_layer = cached
+    out = torch.empty((1, Hq, vc.head_dim), dtype=torch.float32, device=kc.device)
+    sink_probs = None if sink_scores is None else torch.empty_like(sink_scores)
+    ops.decode_step_gqa(cached[1], Hq, kpos, q, k, v, out, sink_scores, v_rep, sink_probs)
+    kc.klen += 1
+    vc.vlen += 1
+    return out, sink_probs
+
+
 def shard_record_floats(H, hd):
     """floats of one shard's record: [H*hd: output normalised over the shard][H x (max, normaliser)]"""
     return H * hd + 2 * H
@@ -681,6 +735,9 @@ def shard_attention(kc, vc, q, k=None, v=None, pos_base=0, record=None, k_sink=N
     (no cached tokens, no new one, no sinks) returns zeros with (M, Z) = (-inf, 0).  Sparse caches with the outlier mirror."""
     if not (kc.include_sparse and vc.include_sparse):
         raise ValueError("shard_attention needs include_sparse caches")
+    if q.dim() != 2 or q.shape[0] != kc.num_heads:
+        raise ValueError("shard_attention: q must be [%d, 128] -- the token-sharded path is MHA only (no grouped-query "
+                         "attention)" % kc.num_heads)
     if (k_sink is None) != (v_sink is None):
         raise ValueError("shard_attention: k_sink and v_sink come together")
     if getattr(kc, "compact", False) or getattr(vc, "compact", False):
@@ -890,6 +947,9 @@ class HeadShard:
         n_sink, 128]): this shard's heads of the fp16 sink caches (first_few_fp16 > 0).  Appends the token (staging column 0
         -> extract) and returns f32 [1, n_heads, hd]: the complete, normalised attention output of this shard's heads over
         all cached tokens (a view of `record` when given).  ONE library call (kvq_head_shard_step)."""
+        if q.dim() != 2 or q.shape[0] not in (self.n_heads, self.num_heads):
+            raise ValueError("HeadShard.attend: q must be [%d or %d, 128] -- the head-sharded path is MHA only (no "
+                             "grouped-query attention)" % (self.n_heads, self.num_heads))
         if (k_sink is None) != (self.first_few_fp16 == 0) or (k_sink is None) != (v_sink is None):
             raise ValueError("HeadShard.attend: pass this shard's k_sink / v_sink exactly when first_few_fp16 > 0")
         if q.shape[0] == self.num_heads and self.n_heads != self.num_heads:

@@ -293,3 +293,77 @@ int kvq_decode_steps(int n_layers, const kvq_layer *layers, int64_t col, const v
 }
 
 }  // extern "C"
+
+// ---- grouped-query attention: one decode token through one layer whose cache holds Hkv = layer->H KV heads ----------
+namespace kvq {
+
+struct GqaPlan {
+  size_t score_ws, parts_off, scores_off, probs_off, mix_off, total;
+  int n_parts;
+};
+
+static GqaPlan plan_gqa(int bits, int Hq, int Hkv, int64_t L) {
+  GqaPlan p;
+  p.score_ws = align256(kvq_score_k_gqa_workspace_bytes(bits, Hq, Hkv));
+  p.n_parts = kvq_score_k_gqa_parts(L);
+  p.parts_off = p.score_ws;
+  p.scores_off = p.parts_off + align256((size_t)Hq * p.n_parts * 8);
+  p.probs_off = p.scores_off + align256((size_t)Hq * L * 4);
+  p.mix_off = p.probs_off + align256((size_t)Hq * L * 4);
+  p.total = p.mix_off + align256(kvq_mix_v_gqa_workspace_bytes(bits, Hq, Hkv, kHeadDim, L));
+  return p;
+}
+
+}  // namespace kvq
+
+extern "C" {
+
+size_t kvq_decode_step_gqa_workspace_bytes(int bits, int Hq, int Hkv, int hd, int64_t L) {
+  if (bits < 2 || bits > 4 || !kvq_gqa_supported(Hq, Hkv, hd) || L <= 0) return 0;
+  return plan_gqa(bits, Hq, Hkv, L).total;
+}
+
+int kvq_decode_step_gqa(const kvq_layer *ly, int Hq, int64_t col, const void *q, const void *k, const void *v,
+                        int acts_are_half, const uint16_t *sink_scores, int n_sink, const uint16_t *v_sink,
+                        uint16_t *sink_probs, float *out, void *workspace, size_t workspace_bytes, void *stream) {
+  // every argument is checked before the first launch: a refused call leaves the cache untouched
+  if (!ly || !q || !k || !v || !out || col < 0) return KVQ_EINVAL;
+  const int bits = ly->bits, Hkv = ly->H, hd = ly->hd;
+  if (bits < 2 || bits > 4 || !kvq_gqa_supported(Hq, Hkv, hd) || ly->thr_k <= 0) return KVQ_EINVAL;
+  // Dense-and-Sparse caches in the reference outlier format with the K mirror (the compact format is not taken)
+  if (!ly->kmat || !ly->klut || !ly->vmat || !ly->vlut_rows || !ly->koutliers_t || !ly->kidx_t || !ly->voutliers ||
+      !ly->vidx || (ly->koutliers && !ly->kidx))
+    return KVQ_EINVAL;
+  const int64_t L = col + 1;
+  // (the shape rules of kvq_score_k_gqa, checked here so that a refused call has not appended yet)
+  if (L > ly->max_len || ly->max_len >= (1ll << 31) || ly->pos_offset < 0) return KVQ_EINVAL;
+  if (n_sink < 0 || (n_sink > 0 && (!sink_scores || !sink_probs)) || (v_sink && n_sink <= 0)) return KVQ_EINVAL;
+  const GqaPlan p = plan_gqa(bits, Hq, Hkv, L);
+  if (!workspace || workspace_bytes < p.total || reinterpret_cast<uintptr_t>(workspace) % 256) return KVQ_EWORKSPACE;
+  unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+  float *parts = reinterpret_cast<float *>(ws + p.parts_off);
+  float *scores = reinterpret_cast<float *>(ws + p.scores_off);
+  float *probs = reinterpret_cast<float *>(ws + p.probs_off);
+  const int n_out = 2 * ly->thr_k;
+  const float inv = 1.0f / sqrtf((float)hd);
+  hipStream_t st = (hipStream_t)stream;
+  struct Clear { ~Clear() { step_events = nullptr; } } clear_events_on_exit;
+  int rc = kvq_append_kv_fused(ly, col, k, v, acts_are_half, stream);
+  if (rc) return rc;
+  record(0, st);
+  rc = kvq_score_k_gqa(bits, q, acts_are_half, ly->kmat, scores, ly->klut_score ? ly->klut_score : ly->klut, Hq, Hkv, hd, L,
+                       ly->max_len, ly->rope_theta, ly->pos_offset, ly->koutliers_t, ly->kidx_t, n_out, inv, parts,
+                       p.n_parts, ws, p.score_ws, stream);
+  record(1, st);
+  if (rc) return rc;
+  rc = kvq_softmax_finish(scores, sink_scores, parts, p.n_parts, probs, sink_probs, Hq, L, n_sink, inv, v_sink, out, stream);
+  if (rc) return rc;
+  record(2, st);
+  rc = kvq_mix_v_gqa(bits, probs, ly->vmat, out, ly->v_mix_rows ? ly->v_mix_rows : ly->vlut_rows, Hq, Hkv, hd, L,
+                     ly->max_len, ly->voutliers, ly->vidx, n_out, v_sink ? 1 : 0, ws + p.mix_off, p.total - p.mix_off,
+                     stream);
+  record(3, st);
+  return rc;
+}
+
+}  // extern "C"

@@ -46,6 +46,7 @@ struct AttnArgs {
   int64_t qsh, qss, ksh, kss, vsh, vss, osh, oss;
   int S, H;
   float scale_log2e;      // softmax scale * log2(e)
+  int G;                  // GQA: query heads per KV head (the GQA instantiation reads K / V of head h / G)
 };
 
 // two floats -> packed fp16, ROUND TO NEAREST (gfx950's v_cvt_pk_f16_f32; cvt_pkrtz truncates, which biases P -- and
@@ -56,6 +57,7 @@ __device__ __forceinline__ uint32_t pack_f16(float a, float b) {
   return r;
 }
 
+template <bool GQA>
 __global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * kStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -68,8 +70,9 @@ __global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kerne
   const int q0 = q0w + wave * kQB;                     // ... of this wave
   const int qrow = q0 + ql;                            // this lane's query row
   const int qrc = qrow < a.S ? qrow : a.S - 1;
-  const f16 *kh = a.k + (int64_t)h * a.ksh;
-  const f16 *vh = a.v + (int64_t)h * a.vsh;
+  const int hk = GQA ? h / a.G : h;                    // KV head of this query head
+  const f16 *kh = a.k + (int64_t)hk * a.ksh;
+  const f16 *vh = a.v + (int64_t)hk * a.vsh;
 
   // ---- Q fragments (B operand of S^T): lane (q, hi) holds Q[q][ks*16 + hi*8 .. +7], ks = 0..7
   f16x8 qf[8];
@@ -232,13 +235,7 @@ __global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kerne
   }
 }
 
-}  // namespace kvq
-
-using namespace kvq;
-
-extern "C" {
-
-int kvq_prefill_attention(const void *q, const void *k, const void *v, void *out, int H, int S, int hd,
+static int prefill_launch(bool gqa, const void *q, const void *k, const void *v, void *out, int H, int G, int S, int hd,
                           int64_t q_stride_h, int64_t q_stride_s, int64_t k_stride_h, int64_t k_stride_s,
                           int64_t v_stride_h, int64_t v_stride_s, int64_t o_stride_h, int64_t o_stride_s,
                           float softmax_scale, void *stream) {
@@ -257,10 +254,35 @@ int kvq_prefill_attention(const void *q, const void *k, const void *v, void *out
   a.vsh = v_stride_h; a.vss = v_stride_s; a.osh = o_stride_h; a.oss = o_stride_s;
   a.S = S;
   a.H = H;
+  a.G = G;
   a.scale_log2e = softmax_scale * 1.4426950408889634f;
   dim3 grid((unsigned)((S + kQW - 1) / kQW) * (unsigned)H), block(kAW * 64);
-  prefill_attn_kernel<<<grid, block, 0, (hipStream_t)stream>>>(a);
+  if (gqa) prefill_attn_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(a);
+  else prefill_attn_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(a);
   return check_launch();
+}
+
+}  // namespace kvq
+
+using namespace kvq;
+
+extern "C" {
+
+int kvq_prefill_attention(const void *q, const void *k, const void *v, void *out, int H, int S, int hd,
+                          int64_t q_stride_h, int64_t q_stride_s, int64_t k_stride_h, int64_t k_stride_s,
+                          int64_t v_stride_h, int64_t v_stride_s, int64_t o_stride_h, int64_t o_stride_s,
+                          float softmax_scale, void *stream) {
+  return prefill_launch(false, q, k, v, out, H, 1, S, hd, q_stride_h, q_stride_s, k_stride_h, k_stride_s, v_stride_h,
+                        v_stride_s, o_stride_h, o_stride_s, softmax_scale, stream);
+}
+
+int kvq_prefill_attention_gqa(const void *q, const void *k, const void *v, void *out, int Hq, int Hkv, int S, int hd,
+                              int64_t q_stride_h, int64_t q_stride_s, int64_t k_stride_h, int64_t k_stride_s,
+                              int64_t v_stride_h, int64_t v_stride_s, int64_t o_stride_h, int64_t o_stride_s,
+                              float softmax_scale, void *stream) {
+  if (Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 8) return KVQ_EINVAL;
+  return prefill_launch(true, q, k, v, out, Hq, Hq / Hkv, S, hd, q_stride_h, q_stride_s, k_stride_h, k_stride_s, v_stride_h,
+                        v_stride_s, o_stride_h, o_stride_s, softmax_scale, stream);
 }
 
 }  // extern "C"

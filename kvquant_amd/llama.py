@@ -21,7 +21,8 @@ What carries over from the reference, by name:
     norm / lm_head on the first (ML:2428-2453), activations moved at the split points (ML:2552-2556, 2583-2585);
   * the quantizer pickle: {"model.layers.N.self_attn.k_proj": (upper, lower, [centroids], [normscale, normoffset])}
     (simquant_module_quantizer.py:550-555), keys containing ".lut" skipped (deployment/llama.py:188-189).
-Batch 1, MHA only, as the reference asserts (ML:1408, 1801).  Prefill attention is the library's own MFMA flash
+Batch 1, as the reference asserts (ML:1801); MHA, and grouped-query attention with 1 <= G <= 8 KV-head groups
+(the reference asserts MHA, ML:1408).  Prefill attention is the library's own MFMA flash
 kernel (kvq_prefill_attention; the reference calls flash-attn there, ML:2013-2070); decode is the GPU-resident kernel
 path of kvquant_amd.cache.decode_kv.
 
@@ -43,7 +44,7 @@ import torch
 import torch.nn as nn
 
 from . import sharding
-from .attention import KVQuantAttention
+from .attention import KVQuantAttention, gqa_groups
 
 KNOBS = dict(dynamicrope=True, use_orig_sparse=False, first_few_fp16=0, maxseqlen=-1, abits=4, include_sparse=False)
 
@@ -63,11 +64,21 @@ def _attn_forward(self, hidden_states, position_embeddings=None, attention_mask=
     bsz, q_len, _ = hidden_states.shape
     core = self.kvq
     shape = (bsz, q_len, core.num_heads, core.head_dim)
+    kv_shape = (bsz, q_len, core.num_key_value_heads, core.head_dim)
     q = self.q_proj(hidden_states).view(shape).transpose(1, 2)
-    k = self.k_proj(hidden_states).view(shape).transpose(1, 2)
-    v = self.v_proj(hidden_states).view(shape).transpose(1, 2)
+    k = self.k_proj(hidden_states).view(kv_shape).transpose(1, 2)
+    v = self.v_proj(hidden_states).view(kv_shape).transpose(1, 2)
     out = core.attend(q, k, v)
     return self.o_proj(out.to(hidden_states.dtype)), None
+
+
+def kv_heads_of(cfg):
+    """the KV head count a patched layer is built with: config.num_key_value_heads (default: num_attention_heads).
+    Grouped-query attention is taken for num_attention_heads = G * num_key_value_heads with 1 <= G <= 8 (the
+    reference's deployment path is MHA only, ML:1408); raises ValueError for other counts."""
+    n_kv = getattr(cfg, "num_key_value_heads", None) or cfg.num_attention_heads
+    gqa_groups(cfg.num_attention_heads, n_kv)
+    return int(n_kv)
 
 
 def patch_llama(model, sparsity_threshold=0.99, compact=False):
@@ -77,8 +88,7 @@ def patch_llama(model, sparsity_threshold=0.99, compact=False):
     GPU-resident paths only, lossy against the reference format by the fp16 rounding of the residuals."""
     cfg = model.config
     kvquant_config(cfg)
-    if getattr(cfg, "num_key_value_heads", cfg.num_attention_heads) != cfg.num_attention_heads:
-        raise ValueError("KVQuant's deployment path is MHA only (ML:1408)")
+    n_kv = kv_heads_of(cfg)
     if cfg.maxseqlen is None or cfg.maxseqlen <= 0:
         raise ValueError("config.maxseqlen must be set (size of the preallocated compressed cache)")
     theta = getattr(cfg, "rope_theta", None)
@@ -91,7 +101,8 @@ def patch_llama(model, sparsity_threshold=0.99, compact=False):
         core = KVQuantAttention(hidden_size=cfg.hidden_size, num_heads=cfg.num_attention_heads, abits=cfg.abits,
                                 include_sparse=cfg.include_sparse, first_few_fp16=cfg.first_few_fp16,
                                 maxseqlen=cfg.maxseqlen, rope_theta=float(theta), sparsity_threshold=sparsity_threshold,
-                                device=dev, dtype=next(attn.parameters()).dtype, make_proj=False, compact=compact)
+                                device=dev, dtype=next(attn.parameters()).dtype, make_proj=False, compact=compact,
+                                num_key_value_heads=None if n_kv == cfg.num_attention_heads else n_kv)
         # plain attributes, like the reference's (ML:1440-1466): they do not follow module.to(); use set_devices
         object.__setattr__(attn, "kvq", core)
         object.__setattr__(attn, "kcache", core.kcache)
@@ -136,6 +147,8 @@ def set_devices(model, devices=None):
     points and back (ML:2552-2556, 2583-2585).  Call BEFORE patch_llama so that the caches are created where their
     layer lives (the reference's .cuda()-pinned caches stay on device 0).  The one-process-per-GPU
     form used for the scaling benchmark is kvquant_amd.sharding.StreamPipeline."""
+    if kv_heads_of(model.config) != model.config.num_attention_heads:
+        raise ValueError("set_devices: the layer-sharded placement is MHA only; this model uses grouped-query attention")
     if devices is None:
         devices = ["cuda:%d" % i for i in range(torch.cuda.device_count())]
     devices = [torch.device(d) for d in devices]

@@ -743,3 +743,99 @@ def head_shard_step(full_layer, shard_layer, h0, col, q, k, v, out, fuse_softmax
             None if sk is None else ctypes.byref(sk), None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
             None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax), base, nb, _stream()),
             "kvq_head_shard_step")
+
+
+# ---- grouped-query attention (GQA): Hq query heads over Hkv KV heads, query head h reads KV head h // G -------------
+def gqa_supported(Hq, Hkv, hd=128):
+    """1 <= G = Hq / Hkv <= 8 (integer), Hkv * hd <= 8192, hd = 128 (include/kvq.h: kvq_gqa_supported)"""
+    return bool(_L().kvq_gqa_supported(int(Hq), int(Hkv), int(hd)))
+
+
+def score_k_gqa(bits, q, mat, mul, lut, L, theta, pos_offset, outliers_t=None, outlier_indices_t=None, inv_sqrt_hd=None,
+                parts=None):
+    """kvq_score_k_gqa: raw scores mul f32 [Hq, L] of q [Hq, 128] (fp32 or fp16) over a cache of Hkv heads; K outliers
+    from the token-contiguous mirror [n_out, max_len] (or none).  parts (optional): f32 [Hq, n_parts, 2] that receives
+    the first softmax pass (n_parts = score_k_gqa_parts(L))."""
+    Hkv, hd, max_len = _cache_dims(mat, bits)
+    qp, qh = _act(q, "q")
+    Hq = q.shape[0]
+    n_out = 0 if outlier_indices_t is None else outlier_indices_t.shape[0]
+    with _Dev(mul):
+        nbytes = _L().kvq_score_k_gqa_workspace_bytes(bits, Hq, Hkv)
+        if nbytes == 0:
+            raise ValueError("score_k_gqa: unsupported shape (Hq=%d, Hkv=%d, bits=%d)" % (Hq, Hkv, bits))
+        ws = _workspace(mul.device, nbytes, slot="gqa_score")
+        _lib.check(_L().kvq_score_k_gqa(
+            bits, qp, qh, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lut"), Hq, Hkv, hd, int(L), max_len, float(theta),
+            int(pos_offset), _fo(outliers_t, "outliers_t"), _io(outlier_indices_t, "outlier_indices_t"), n_out,
+            float(inv_sqrt_hd if inv_sqrt_hd is not None else 1.0 / hd ** 0.5),
+            None if parts is None else _f(parts, "parts"), 0 if parts is None else parts.shape[1],
+            ws.data_ptr(), ws.numel(), _stream()), "kvq_score_k_gqa")
+    return mul
+
+
+def score_k_gqa_parts(L):
+    return _L().kvq_score_k_gqa_parts(int(L))
+
+
+def mix_v_gqa(bits, p, mat, mul, lut_rows, L, outliers=None, outlier_indices=None, accumulate=False):
+    """kvq_mix_v_gqa: mul f32 [Hq, 128] (+)= p f32 [Hq, L] . Vhat of KV head h // G; V outliers in the reference rows."""
+    Hkv, hd, max_len = _cache_dims(mat, bits)
+    Hq = p.shape[0]
+    n_out = 0 if outlier_indices is None else outlier_indices.shape[1]
+    with _Dev(mul):
+        nbytes = _L().kvq_mix_v_gqa_workspace_bytes(bits, Hq, Hkv, hd, int(L))
+        if nbytes == 0:
+            raise ValueError("mix_v_gqa: unsupported shape (Hq=%d, Hkv=%d, bits=%d, L=%d)" % (Hq, Hkv, bits, L))
+        ws = _workspace(mul.device, nbytes, slot="gqa_mix")
+        _lib.check(_L().kvq_mix_v_gqa(
+            bits, _f(p, "p"), _i(mat, "mat"), _f(mul, "mul"), _f(lut_rows, "lut_rows"), Hq, Hkv, hd, int(L), max_len,
+            _fo(outliers, "outliers"), _io(outlier_indices, "outlier_indices"), n_out, 1 if accumulate else 0,
+            ws.data_ptr(), ws.numel(), _stream()), "kvq_mix_v_gqa")
+    return mul
+
+
+def decode_step_gqa(layer, Hq, col, q, k, v, out, sink_scores=None, v_sink=None, sink_probs=None):
+    """kvq_decode_step_gqa: append + grouped q.K^T + softmax + grouped p.V of one layer from ONE library call.
+    layer: struct from make_layer (layer.H = KV heads); q [Hq, 128], k, v [Hkv*128]: all fp16 or all fp32; out f32
+    [1, Hq, hd].  sink_scores: fp16 [Hq, n_sink] already scaled (sink_probs receives their probabilities);
+    v_sink: fp16 [Hq, n_sink, 128], then out also holds the sink tokens' share."""
+    kp, kh = _act(k, "k")
+    vp, vh = _act(v, "v")
+    qp, qh = _act(q, "q")
+    if not (kh == vh == qh):
+        raise ValueError("q, k, v must share one dtype (fp32 or fp16)")
+    n_sink = 0 if sink_scores is None else sink_scores.shape[1]
+    with _Dev(out):
+        nbytes = _L().kvq_decode_step_gqa_workspace_bytes(layer.bits, int(Hq), layer.H, layer.hd, int(col) + 1)
+        if nbytes == 0:
+            raise ValueError("decode_step_gqa: unsupported shape (Hq=%d, Hkv=%d)" % (Hq, layer.H))
+        ws = _workspace(out.device, nbytes + 256, slot="step")
+        base = (ws.data_ptr() + 255) & ~255
+        _lib.check(_L().kvq_decode_step_gqa(
+            ctypes.byref(layer), int(Hq), int(col), qp, kp, vp, kh,
+            None if sink_scores is None else _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
+            None if sink_probs is None else _chk(sink_probs, torch.float16, "sink_probs"), _f(out, "out"),
+            base, ws.numel() - (base - ws.data_ptr()), _stream()), "kvq_decode_step_gqa")
+
+
+def prefill_attention_gqa(q, k, v, softmax_scale=None):
+    """causal attention of a prompt with grouped KV heads: q fp16 [Hq, S, 128], k, v fp16 [Hkv, S, 128] views (any
+    strides with a contiguous last dimension); query head h attends with KV head h // (Hq / Hkv).
+    -> fp16 [S, Hq*128] (token-major, ready for o_proj)."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(2) == 1):
+            raise ValueError("%s: expected an fp16 GPU tensor [H, S, head_dim] with a contiguous last dimension" % name)
+    Hq, S, hd = q.shape
+    Hkv = k.shape[0]
+    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or Hkv <= 0 or Hq % Hkv or not 1 <= Hq // Hkv <= 8:
+        raise ValueError("prefill_attention_gqa: q [Hq, S, hd], k / v [Hkv, S, hd] with Hq = G * Hkv, 1 <= G <= 8")
+    out = torch.empty((S, Hq, hd), dtype=torch.float16, device=q.device)
+    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / (hd ** 0.5)
+    with _Dev(q):
+        _lib.check(_L().kvq_prefill_attention_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), Hq, Hkv, S,
+                                                 hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
+                                                 v.stride(1), out.stride(1), out.stride(0), scale, _stream()),
+                   "kvq_prefill_attention_gqa")
+    return out.view(S, Hq * hd)

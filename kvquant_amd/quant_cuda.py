@@ -80,6 +80,15 @@ def _shadow_mirror(outliers, outlier_indices, L, stream=None, transpose=None):
     return s
 
 
+def _mha_only(vec, mat):
+    """the module swap replaces the reference's MHA-only extension: a query with another head count than the cache (the
+    heads of a grouped-query attention model) is refused instead of read against the wrong KV heads"""
+    if vec.dim() != 3 or mat.dim() != 3 or vec.shape[1] != mat.shape[0]:
+        raise ValueError("quant_cuda: vec has %s heads, the cache %d -- the module swap is MHA only; grouped-query "
+                         "attention goes through kvquant_amd.cache.decode_kv"
+                         % (tuple(vec.shape[1:2]), mat.shape[0] if mat.dim() == 3 else -1))
+
+
 def _make(bits):
     ns = {}
 
@@ -110,9 +119,11 @@ def _make(bits):
                                    outlier_threshold_upper, 0)
 
     def k_opt(vec, mat, mul, lookup_table, kcachelen, theta, pos_offset):
+        _mha_only(vec, mat)
         ops.score_k(bits, vec, mat, mul, lookup_table, kcachelen, theta, pos_offset)
 
     def k_opt2(vec, mat, mul, lookup_table, kcachelen, outliers, outlier_indices, theta, pos_offset):
+        _mha_only(vec, mat)
         if QC_MIRROR and vec.shape[0] == 1 and kcachelen >= QC_MIRROR_FROM and outliers.dim() == 2 and \
                 outliers.dtype == torch.float32 and outlier_indices.dtype == torch.int32 and \
                 outliers.is_contiguous() and outlier_indices.is_contiguous() and \
@@ -124,9 +135,11 @@ def _make(bits):
         ops.score_k(bits, vec, mat, mul, lookup_table, kcachelen, theta, pos_offset, outliers, outlier_indices)
 
     def v_opt(vec, mat, mul, lookup_table, vcachelen):
+        _mha_only(vec, mat)
         ops.mix_v(bits, vec, mat, mul, lookup_table, vcachelen)
 
     def v_opt2(vec, mat, mul, lookup_table, vcachelen, outliers, outlier_indices):
+        _mha_only(vec, mat)
         ops.mix_v(bits, vec, mat, mul, lookup_table, vcachelen, outliers, outlier_indices)
 
     b = str(bits)
