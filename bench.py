@@ -12,6 +12,9 @@ fp16 activations) and the caches are resident in HBM before the timed region.
 The model's linear layers are NOT part of this path.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--ctx 131072] [--bits 4] [--sinks 0]
+                                   # the headline alone: set up, warm up, time K steps, print the JSON line
+  python bench.py ... --full       # + what the headline does not need: the other BASELINE configurations (`configs`),
+                                   # the full-model leg, the fp16 and CPU baselines (each skippable with its --no-* option)
   python bench.py ... --dump-outputs DIR   # also write the last timed step's attention outputs as DIR/attn_out.npy
   python bench.py --sweep          # one JSON line per BASELINE configuration (4K hot/rotated, 32K, 128K, 1M;
                                    # nuq4 and nuq3 + 5 sinks), the default line last
@@ -72,13 +75,17 @@ def parse():
     ap.add_argument("--retrieval", action="store_true", help="plant a retrievable token and check it (config 5 proxy)")
     ap.add_argument("--time-every", type=int, default=11,
                     help="bracket every N-th layer's two matvec launches with HIP events (1 = all; the events cost time)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs it does not need (off by default): the other BASELINE "
+                         "configurations under `configs` (1 GPU), the full-model leg, the fp16 and CPU baselines")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the short legs over the other BASELINE configurations that the default 1-GPU line carries "
+                    help="--full: skip the short legs over the other BASELINE configurations that the 1-GPU line carries "
                          "under `configs` (4K / 32K decode, nuq3 + 5 sinks at 128K, the 8K prefill, 1M tokens on one GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp16-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fp16-baseline", action="store_true", help="--full: skip the fp16 matvec baseline")
     ap.add_argument("--no-full-model", action="store_true",
-                    help="skip the full-model leg (random-init LLaMA-2-7B-shaped fp16 weights over the same filled caches)")
+                    help="--full: skip the full-model leg (random-init LLaMA-2-7B-shaped fp16 weights over the same filled "
+                         "caches)")
     ap.add_argument("--cpu-sample-tokens", type=int, default=8192)
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one returned to its caller -- every layer's attention "
@@ -995,7 +1002,7 @@ def run_config(args, rank, world, dev, dist, label=None, with_baselines=True):
 
 
 def config_summary(r):
-    """one BASELINE configuration of the `configs` list of the default line: what the headline reports, in short"""
+    """one BASELINE configuration of the `configs` list of the --full line: what the headline reports, in short"""
     k = r.get("kernels", {})
     out = {"label": r["config"].get("label"), "workload": r["config"]["workload"], "value": r["value"], "unit": r["unit"],
            "ms_per_step": r["ms_per_step"], "steps": r["steps"],
@@ -1014,7 +1021,7 @@ def config_summary(r):
 
 
 def other_configs(args, rank, world, dev, dist):
-    """The BASELINE configurations besides the headline, as short legs of the default run: config 2
+    """The BASELINE configurations besides the headline, as short legs of a --full run: config 2
     (4K / 32K decode), config 3 (nuq3 + 5 fp16 sink tokens at 128K), config 4 (8K-token prefill: pack + MFMA attention)
     and the 1M-token shape of config 5 on one GPU (8 of its 32 layers).  Same code path as the headline (run_config),
     fewer steps, no baselines; `frac` is the dominant kernel's fraction of 8 TB/s from its in-stream event timers."""
@@ -1131,8 +1138,9 @@ def main():
     elif args.shard == "heads":
         res = run_head_sharded(args, rank, world, dev, dist)
     else:
-        res = run_config(args, rank, world, dev, dist)
-        if world == 1 and res is not None and not args.no_configs and not args.retrieval:
+        # (a plain run stops at the headline; --full adds the baselines and the other configurations after it)
+        res = run_config(args, rank, world, dev, dist, with_baselines=args.full)
+        if args.full and world == 1 and res is not None and not args.no_configs and not args.retrieval:
             res["configs"] = other_configs(args, rank, world, dev, dist)
     if rank == 0:
         print(json.dumps(res), flush=True)

@@ -24,7 +24,8 @@ def _run(*args):
 def test_bench_line_contract():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    d = _run("--ctx", "2048", "--layers", "2", "--steps", "3", "--warmup", "1", "--cpu-sample-tokens", "256", "--no-configs")
+    d = _run("--ctx", "2048", "--layers", "2", "--steps", "3", "--warmup", "1", "--cpu-sample-tokens", "256", "--no-configs",
+             "--full")
     assert "configs" not in d
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline", "kernels", "full_model", "fp16_baseline"):
@@ -45,12 +46,12 @@ def test_bench_line_contract():
 
 
 def test_bench_line_carries_every_baseline_config():
-    """The default 1-GPU line carries the other BASELINE configurations as short legs under `configs`:
+    """The 1-GPU --full line carries the other BASELINE configurations as short legs under `configs`:
     config 2 at 4K and 32K, config 3 (nuq3 + 5 sinks at 128K), the 1M-token shape of config 5 on one GPU, config 4 (prefill)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     d = _run("--ctx", "2048", "--layers", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-fp16-baseline",
-             "--no-full-model")
+             "--no-full-model", "--full")
     cfgs = d["configs"]
     assert len(cfgs) == 5, [c.get("label") for c in cfgs]
     for c in cfgs:
@@ -63,6 +64,20 @@ def test_bench_line_carries_every_baseline_config():
     assert all(("score_k_us" in c and "mix_v_us" in c) or "fused_attend_us" in c for c in decode), decode
     pre = [c for c in cfgs if "prefill" in c["label"]][0]
     assert pre["pack_k_us"] > 0 and pre["pack_v_us"] > 0 and pre["prefill_attention_TFLOPs"] > 0
+
+
+def test_bench_plain_line_is_headline_only():
+    """Without --full the line is the headline alone: its fields and roofline, none of the legs that run after it"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    d = _run("--ctx", "2048", "--layers", "2", "--steps", "3", "--warmup", "1")
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+                "roofline", "kernels"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1000.0 - 1.0) < 1e-6
+    for key in ("configs", "cpu_baseline", "fp16_baseline", "full_model"):
+        assert key not in d, key
 
 
 def test_bench_head_sharded_single_rank():

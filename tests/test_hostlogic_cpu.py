@@ -64,6 +64,19 @@ def test_bench_event_sampling_covers_all_layers():
     assert timed == set(range(32))
 
 
+def test_bench_full_is_opt_in():
+    """a plain bench.py run is the headline alone; the baselines and the other configurations need --full"""
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        assert bench.parse().full is False
+        sys.argv = ["bench.py", "--full"]
+        assert bench.parse().full is True
+    finally:
+        sys.argv = argv
+
+
 def test_quant_cuda_shadow_mirror_decisions():
     """which rows kvquant_amd.quant_cuda transposes into its shadow mirror before an `_opt2` call: one
     row after the reference glue's append (one in-place write per array, ML:748-749), everything whenever older rows may
