@@ -73,6 +73,8 @@ extern "C" {
  *   403  grouped-query attention (GQA): new entries kvq_gqa_supported, kvq_score_k_gqa[_workspace_bytes, _parts],
  *        kvq_mix_v_gqa[_workspace_bytes], kvq_decode_step_gqa[_workspace_bytes], kvq_prefill_attention_gqa.  Every
  *        existing entry point, struct and behaviour is unchanged.
+ *        Later in 403: kvq_chunk_attention[_workspace_bytes] (attention of a multi-token chunk over the compressed
+ *        cache).  Additive only, so kvq_version() stays 403: a caller that needs them looks the symbols up.
  *        A binding checks `kvq_version() / 100 == KVQ_ABI_MAJOR`. */
 #define KVQ_ABI_MAJOR 4
 KVQ_API int kvq_version(void);
@@ -587,6 +589,25 @@ KVQ_API int kvq_prefill_attention_gqa(const void *q, const void *k, const void *
                                       int64_t q_stride_h, int64_t q_stride_s, int64_t k_stride_h, int64_t k_stride_s,
                                       int64_t v_stride_h, int64_t v_stride_s, int64_t o_stride_h, int64_t o_stride_s,
                                       float softmax_scale, void *stream);
+
+/* ---- a chunk of S new tokens over the compressed cache (multi-turn prompts, draft verification, chunked fills) ------
+ * The chunk's K / V are already packed into columns c0 .. c0+S-1 of the layer's caches (kvq_pack_k_fused /
+ * kvq_pack_v_fused with col0 = c0).  Query i < S (RoPE'd at position layer->pos_offset + c0 + i) attends to the n_sink fp16
+ * sink tokens and to the compressed columns [0, c0 + i]:
+ *   out[i][h][:] = sum_t softmax_t(q[h][i] . Khat[h/G][:, t] / sqrt(128)) Vhat[h/G][t][:]
+ * Khat: layer->klut_score (or klut) [code] + the K outlier entries of the mirror koutliers_t / kidx_t, rotated at the
+ * column's position with the angle rule of kvq_score_k; Vhat: layer->v_mix_rows (or vlut_rows) [t][code] + the V outlier
+ * rows voutliers / vidx.  Sinks: k_sink fp16 [Hkv][128][n_sink] (post-RoPE), v_sink fp16 [Hkv][n_sink][128], 0 <= n_sink
+ * <= 64.  Query head h reads KV head h / G, G = Hq / layer->H, 1 <= G <= 8.  q: fp16 [Hq][S][128] at h * q_stride_h +
+ * i * q_stride_s (elements; multiples of 8, q 16-byte aligned).  out: f32 [S][Hq][128], 16-byte aligned.  MFMA flash
+ * kernel with fp16 operands and fp32 accumulation; the column range is split across workgroups and the splits merged
+ * in a fixed order (deterministic).  1 <= S <= 65536, c0 + S <= max_len; every violation is KVQ_EINVAL before any
+ * launch.  workspace: kvq_chunk_attention_workspace_bytes(Hq, Hkv, S, c0) bytes (0: unsupported shape), 256-byte
+ * aligned, else KVQ_EWORKSPACE. */
+KVQ_API size_t kvq_chunk_attention_workspace_bytes(int Hq, int Hkv, int S, int64_t c0);
+KVQ_API int kvq_chunk_attention(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                                int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- uncapped ("orig") Dense-and-Sparse variants, 4 bit only ------------------ */
 

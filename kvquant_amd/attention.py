@@ -15,13 +15,31 @@ token, ML:707-714 and 1803-1820).  Prefill attention is kvq_prefill_attention (M
 flash kernel, csrc/kvq_prefill_attn.hip) where the reference calls flash-attn.
 """
 import math
+import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .cache import QuantK, QuantV, decode_kv
+from .cache import QuantK, QuantV, chunk_kv, decode_kv
+
+# q_len > 1 on a warm cache (multi-turn prompts, draft verification, chunked fills) takes kvq_chunk_attention
+# (cache.chunk_kv).  KVQ_CHUNK_ATTEND=0 feeds such chunks through the q_len == 1 path token by token instead (A/B runs).
+CHUNK_ATTEND = os.environ.get("KVQ_CHUNK_ATTEND", "1") != "0"
+
+
+def chunk_route(klen, q_len, sinks, fast):
+    """How attend() feeds q_len tokens into a cache holding klen > 0 tokens: [(kind, n), ...] in order, kind "token"
+    (n tokens one at a time through the q_len == 1 path) or "chunk" (n >= 2 tokens through chunk_kv).  Tokens that
+    still fill the fp16 sink cache go one at a time; the rest is one chunk when `fast` (the configuration has the
+    kernel) and more than one token remains."""
+    fill = min(max(sinks - klen, 0), q_len)
+    route = [("token", fill)] if fill else []
+    rest = q_len - fill
+    if rest:
+        route.append(("chunk", rest) if (fast and rest >= 2) else ("token", rest))
+    return route
 
 
 def rotate_half(x):
@@ -148,6 +166,8 @@ class KVQuantAttention(nn.Module):
             return self.attend_gqa(query_states, key_states, value_states)
         bsz, H, q_len, hd = query_states.shape
         assert bsz == 1, "batch 1 only (ML:1801)"
+        if q_len > 1 and self.kcache.klen > 0:
+            return self.attend_multi(query_states, key_states, value_states)
         sinks = self.first_few_fp16
         key_states = key_states.half()
         value_states = value_states.half()
@@ -235,6 +255,8 @@ class KVQuantAttention(nn.Module):
         heads + one kvq_decode_step_gqa; the sink-filling phase in torch with the KV heads repeated per group."""
         bsz, H, q_len, hd = query_states.shape
         assert bsz == 1, "batch 1 only (ML:1801)"
+        if q_len > 1 and self.kcache.klen > 0:
+            return self.attend_multi(query_states, key_states, value_states)
         G = self.num_kv_groups
         sinks = self.first_few_fp16
         key_states = key_states.half()
@@ -282,6 +304,51 @@ class KVQuantAttention(nn.Module):
         self.vcache.vlen += 1
         out = torch.matmul(w, self.vcache_fp16[:, :, :self.vcache.vlen, :].repeat_interleave(G, dim=1))
         return out.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
+
+    # ------------------------------------------------------------------ q_len > 1 on a warm cache
+    def chunk_fast(self, query_states):
+        """True if a chunk of this layer can take kvq_chunk_attention: Dense-and-Sparse caches in the reference outlier
+        format (not compact, not the uncapped CSR variants), fp16 activations, head_dim 128, fp16 sink caches."""
+        kc, vc, sinks = self.kcache, self.vcache, self.first_few_fp16
+        return (CHUNK_ATTEND and kc.include_sparse and vc.include_sparse and not kc.compact and not vc.compact
+                and not getattr(kc, "use_orig_sparse", False) and query_states.dtype == torch.float16
+                and self.head_dim == 128 and (sinks == 0 or self.kcache_fp16.dtype == torch.float16))
+
+    def attend_multi(self, query_states, key_states, value_states):
+        """q_len > 1 tokens into a cache that already holds klen > 0 tokens (a follow-up prompt, a draft to verify, the
+        next piece of a chunked fill): the positions continue at klen.  Tokens that still fill the fp16 sink cache go
+        one at a time through the q_len == 1 path, the rest through chunk_kv (the chunk's own tokens are attended AS
+        STORED, compressed, like token-by-token decoding) -- or one at a time where chunk_fast() is False."""
+        q_len = query_states.shape[2]
+        route = chunk_route(self.kcache.klen, q_len, self.first_few_fp16, self.chunk_fast(query_states))
+        outs, i = [], 0
+        for kind, n in route:
+            sl = slice(i, i + n)
+            if kind == "chunk":
+                outs.append(self._attend_chunk(query_states[:, :, sl], key_states[:, :, sl], value_states[:, :, sl]))
+            else:
+                for j in range(i, i + n):
+                    t = slice(j, j + 1)
+                    outs.append(self.attend(query_states[:, :, t], key_states[:, :, t], value_states[:, :, t]))
+            i += n
+        return torch.cat([o.to(query_states.dtype) for o in outs], dim=1)
+
+    def _attend_chunk(self, query_states, key_states, value_states):
+        """one chunk (q_len >= 2, klen >= sinks) through chunk_kv: query RoPE in torch's fp16 roundings (as
+        kvq_rope_q_f16 does for one token), pack + kvq_chunk_attention"""
+        bsz, H, q_len, hd = query_states.shape
+        start = self.kcache.klen
+        cos, sin = self.rotary_emb(value_states, start, start + q_len)
+        query_rope = (query_states * cos) + (rotate_half(query_states) * sin)
+        sinks = self.first_few_fp16
+        k = key_states[0].half().transpose(1, 2)
+        v = value_states[0].half().transpose(1, 2)
+        if sinks > 0:
+            out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v, k_sink=self.kcache_fp16[0],
+                           v_sink=self.vcache_fp16[0])
+        else:
+            out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v)
+        return out.to(query_states.dtype).view(bsz, q_len, self.hidden_size)
 
     def forward(self, hidden_states):
         """hidden_states [1, q_len, hidden] -> [1, q_len, hidden]."""

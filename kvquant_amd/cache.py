@@ -712,6 +712,54 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     return out, sink_probs
 
 
+CHUNK_PIECE = 4096      # query rows per kvq_chunk_attention call (bounds its partials workspace)
+
+
+def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
+    """A chunk of S >= 1 new tokens through a layer's compressed KV path (multi-turn follow-up prompts, draft
+    verification, chunked fills): the chunk's K / V are packed into compressed columns c0 .. c0+S-1, c0 = klen - sinks
+    (parallel_pack: the fused packs, bit-identical to S decode appends), then ONE kvq_chunk_attention call (MFMA flash
+    kernel that decodes the packed tiles itself) attends query i to the fp16 sink tokens and to columns [0, c0 + i].
+    q: fp16 [Hq, S, 128] RoPE'd at positions klen .. klen+S-1 (any strides with a contiguous last dimension); k, v:
+    [Hkv, 128, S] pre-RoPE (as parallel_pack).  k_sink (f16 [Hkv, 128, n_sink], post-RoPE) / v_sink (f16 [Hkv, n_sink,
+    128]): the fp16 sink caches, required when the caches count sink tokens.  Hq = G * Hkv, 1 <= G <= 8.
+    Returns f32 [S, Hq, 128].  Dense-and-Sparse caches in the reference outlier format (not compact) only."""
+    if not (kc.include_sparse and vc.include_sparse):
+        raise ValueError("chunk_kv needs include_sparse caches")
+    if getattr(kc, "compact", False) or getattr(vc, "compact", False) or getattr(kc, "use_orig_sparse", False):
+        raise ValueError("chunk_kv reads the reference outlier format with the K mirror; compact / orig caches go "
+                         "through decode_kv one token at a time")
+    sinks = kc.first_few_fp16
+    if kc.klen != vc.vlen or kc.klen < sinks:
+        raise ValueError("chunk_kv: K / V caches must be in step and past their %d sink tokens" % sinks)
+    if sinks > 0 and (k_sink is None or v_sink is None or int(k_sink.shape[2]) != sinks):
+        raise ValueError("chunk_kv: the caches count %d fp16 sink tokens -- pass k_sink / v_sink holding them" % sinks)
+    Hq, S = int(q.shape[0]), int(q.shape[1])
+    if Hq % kc.num_heads or not 1 <= Hq // kc.num_heads <= 8:
+        raise ValueError("chunk_kv: q has %d heads, the caches %d KV heads (Hq = G * Hkv, 1 <= G <= 8)" % (Hq, kc.num_heads))
+    c0 = kc.klen - sinks
+    if c0 + S > kc.max_len:
+        raise ValueError("chunk_kv: %d + %d tokens exceed the cache (%d columns)" % (c0, S, kc.max_len))
+    kc.parallel_pack(k)
+    vc.parallel_pack(v)
+    lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
+    table = kc.lookup_table2 if (kc.norm and kc.bits == 2) else kc.lookup_table
+    key = (id(vc), getattr(vc, "_tables_version", 0), vc.reference_tie_quirk, vc.norm, kc.norm, kc.compact, vc.compact,
+           kc.score_f16_pair, getattr(kc, "score_f32_pair", False))
+    cached = getattr(kc, "_step_layer", None)
+    if cached is None or cached[0] != key:
+        cached = (key,) + ops.make_layer(kc, vc, table, lut_off)
+        kc._step_layer = cached
+    out = torch.empty((S, Hq, kc.head_dim), dtype=torch.float32, device=kc.device)
+    ks = None if sinks == 0 else k_sink.contiguous()
+    vs = None if sinks == 0 else v_sink.contiguous()
+    # (query rows past a piece see only columns up to their own: a later piece is the same call with c0 moved on)
+    for s0 in range(0, S, CHUNK_PIECE):
+        n = min(CHUNK_PIECE, S - s0)
+        ops.chunk_attention(cached[1], Hq, c0 + s0, q[:, s0:s0 + n], out[s0:s0 + n], ks, vs)
+    return out
+
+
 def shard_record_floats(H, hd):
     """floats of one shard's record: [H*hd: output normalised over the shard][H x (max, normaliser)]"""
     return H * hd + 2 * H

@@ -1,0 +1,452 @@
+// Attention of a chunk of S new tokens over the COMPRESSED cache on the matrix cores (ABI 404): multi-turn follow-up
+// prompts, draft verification and chunked fills after the first chunk.  The chunk has already been packed into columns
+// c0 .. c0+S-1 by the fused packs; query i (RoPE'd at position sinks + c0 + i) attends to the fp16 sink tokens and to the
+// compressed columns [0, c0 + i].
+//
+// Structure of kvq_prefill_attn.hip (fp16 operands on v_mfma_f32_32x32x16_f16, fp32 accumulation, online softmax, no
+// S x L matrix in memory, both products computed transposed so that a lane owns one query row); what differs is where the
+// K / V tiles come from.  Per 64-column tile the workgroup (8 waves = 256 query rows of one query head) decodes the tile
+// itself, once for its 256 rows:
+//   P0  the tile's V codebook rows -> LDS; every thread loads the packed words of its (column, 32-channel group)
+//       (token-contiguous rows: a wave reads 64 consecutive columns of one word row -- coalesced);
+//   P1  waves 0-3: K codes -> the head's per-channel codebook (LDS) -> fp32 K stage; waves 4-7: V codes -> the column's
+//       own codebook row -> fp32 V stage;
+//   P2  outlier residuals of this KV head added into the stages (K: token-contiguous mirror [n_out][max_len], V: reference
+//       rows [max_len][n_out]; ids are global channels);
+//   P3  waves 0-3: RoPE of each (k, k+64) pair at the column's position (sincos_rev, the angle rule of the decode
+//       kernels) -> fp16 K tile in the XOR-swizzled layout of the prefill kernel; waves 4-7: fp16 V^T tile;
+//   then S^T = K.Q^T, mask, online softmax, O^T += V^T.P^T exactly as the prefill kernel.
+// The fp16 sink tokens (post-RoPE K [Hkv][128][n_sink], V [Hkv][n_sink][128]) are one prefix tile without decode.
+// The causal mask is evaluated only on tiles that reach past the wave's first row (c0 + q0) or past the last column.
+//
+// Parallelism: (query head x 256-row block) is 64 workgroups at Hq = 32, S = 512, so the column range is also split
+// across workgroups; each split writes (max, sum, unnormalised O) partials and chunk_attn_merge_kernel merges the splits
+// of a row in a fixed order (deterministic).  GQA: query head h reads KV head h / G (the tile is decoded per query head).
+#include "kvq_common.h"
+#include "kvq_host.h"
+
+namespace kvq {
+namespace chunk {
+
+typedef _Float16 f16;
+typedef f16 f16x8 __attribute__((ext_vector_type(8)));
+typedef f16 f16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kD = 128;            // head_dim
+constexpr int kQB = 32;            // query rows per wave
+constexpr int kAW = 8;             // waves per workgroup
+constexpr int kThreads = kAW * 64;
+constexpr int kQW = kQB * kAW;     // query rows per workgroup
+constexpr int kKV = 64;            // columns per tile
+constexpr int kKRow = kD * 2;      // bytes of a K row in LDS
+constexpr int kVRow = 136;         // bytes of a V^T row in LDS (64 keys x 2 B + 8 pad)
+constexpr int kSR = kD + 4;        // floats per column of the fp32 stages
+constexpr int kMaxSink = 64;       // the sink tokens fit one tile
+constexpr int kTargetWorkgroups = 512;
+constexpr int kMinTilesPerSplit = 4;
+constexpr int kMaxSplits = 64;
+constexpr int kMaxS = 65536;
+constexpr size_t kMaxWorkspace = size_t(1) << 30;
+
+struct Args {
+  const int32_t *kmat, *vmat;
+  const float *klut;                 // [Hkv][128][2^bits]: the table the scores dequantise with
+  const float *kout_t;               // K outlier mirror [n_out][max_len]
+  const int32_t *kidx_t;
+  const float *vrows;                // [max_len][2^bits]: the rows p.V dequantises with
+  const float *vout;                 // V outlier rows [max_len][n_out]
+  const int32_t *vidx;
+  const f16 *q;                      // [Hq][S][128] at h * qsh + s * qss
+  int64_t qsh, qss;
+  const f16 *k_sink, *v_sink;        // [Hkv][128][n_sink], [Hkv][n_sink][128]
+  float *part_o, *part_ml;           // [Hq][nsplit][S][128], [Hq][nsplit][S][2]
+  int64_t max_len, c0;
+  int Hq, G, S, n_sink, n_out, pos_offset, nqb, nsplit, tps;
+  float rope_theta, scale_log2e;
+};
+
+__device__ __forceinline__ uint32_t pack_f16(float a, float b) {
+  uint32_t r;
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
+  constexpr int N = 1 << BITS;
+  constexpr int WPH = kD / 32 * BITS;
+  __shared__ float klut[kD * N];
+  __shared__ float theta[64];
+  __shared__ float vrow[kKV * (N + 1)];
+  __shared__ __attribute__((aligned(16))) float kst[kKV * kSR];
+  __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];
+  __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow];
+  __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hi = lane >> 5, ql = lane & 31;
+  const int split = (int)blockIdx.x % a.nsplit;
+  const int rest = (int)blockIdx.x / a.nsplit;
+  const int h = rest % a.Hq;
+  const int qb = a.nqb - 1 - rest / a.Hq;              // late (long-row) query blocks first
+  const int hk = h / a.G;
+  const int q0w = qb * kQW;
+  const int q0 = q0w + wave * kQB;
+  const int qrow = q0 + ql;
+  const int qrc = qrow < a.S ? qrow : a.S - 1;
+  const int64_t ml = a.max_len;
+  const int64_t Lc = a.c0 + a.S;                       // compressed columns after the append
+  const int rows_end = (q0w + kQW < a.S) ? q0w + kQW : a.S;
+  const int64_t kend = a.c0 + rows_end;                // columns [0, kend) matter to this workgroup
+  const int n_tiles = (int)((kend + kKV - 1) / kKV);
+  const int t_beg = split * a.tps;
+  const int t_end = (t_beg + a.tps < n_tiles) ? t_beg + a.tps : n_tiles;
+  const bool with_sinks = split == 0 && a.n_sink > 0;
+
+  for (int e = tid; e < kD * N; e += kThreads) klut[e] = a.klut[(int64_t)hk * kD * N + e];
+  if (tid < 64) theta[tid] = rope_freq(a.rope_theta, tid);
+
+  // ---- Q fragments (B operand of S^T): lane (q, hi) holds Q[q][ks*16 + hi*8 .. +7]
+  f16x8 qf[8];
+  {
+    const f16 *qp = a.q + (int64_t)h * a.qsh + (int64_t)qrc * a.qss + hi * 8;
+#pragma unroll
+    for (int ks = 0; ks < 8; ks++) qf[ks] = *reinterpret_cast<const f16x8 *>(qp + ks * 16);
+  }
+  f32x16 oacc[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) oacc[i][r] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+
+  // ---- S^T, mask, online softmax, O^T of one staged tile.  sink: key j of the tile is sink token j (no causal mask);
+  // else key j is compressed column t0 + j, visible to row q iff t0 + j <= c0 + q (and < Lc)
+  auto attend_tile = [&](bool sink, int64_t t0) __attribute__((always_inline)) {
+    const bool active = q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1);
+    if (!active) return;
+    f32x16 sacc[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; kb++) {
+#pragma unroll
+      for (int r = 0; r < 16; r++) sacc[kb][r] = 0.f;
+      const int key = kb * 32 + ql;
+#pragma unroll
+      for (int kk = 0; kk < 8; kk++) {
+        const int c = kk * 2 + hi;
+        const f16x8 kf = *reinterpret_cast<const f16x8 *>(k16 + key * kKRow + ((c ^ (key & 15)) << 4));
+        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sacc[kb], 0, 0, 0);
+      }
+    }
+    const bool diag = sink ? a.n_sink < kKV : (t0 + kKV - 1 > a.c0 + q0 || t0 + kKV > Lc);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        float s = sacc[kb][r];
+        if (diag) {
+          const int j = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const bool vis = sink ? j < a.n_sink : (t0 + j <= a.c0 + qrow && t0 + j < Lc);
+          if (!vis) s = -INFINITY;
+          sacc[kb][r] = s;
+        }
+        mx = fmaxf(mx, s);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new;
+    const float mc = -m_use * a.scale_log2e;
+    float ps = 0.f;
+    uint32_t pp[2][8];
+#pragma unroll
+    for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], a.scale_log2e, mc));
+        const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r + 1], a.scale_log2e, mc));
+        ps += p0 + p1;
+        pp[kb][r >> 1] = pack_f16(p0, p1);
+      }
+    ps += __shfl_xor(ps, 32);
+    if (__any(m_new != m_run)) {
+      const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * a.scale_log2e);
+      l_run *= alpha;
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) oacc[i][r] *= alpha;
+    }
+    l_run += ps;
+    m_run = m_new;
+#pragma unroll
+    for (int kb = 0; kb < 2; kb++)
+#pragma unroll
+      for (int ks2 = 0; ks2 < 2; ks2++) {
+        const u32x4 pw = {pp[kb][ks2 * 4], pp[kb][ks2 * 4 + 1], pp[kb][ks2 * 4 + 2], pp[kb][ks2 * 4 + 3]};
+        const f16x8 pf = __builtin_bit_cast(f16x8, pw);
+        const int kofs = (kb * 32 + ks2 * 16 + 4 * hi) * 2;
+#pragma unroll
+        for (int db = 0; db < 4; db++) {
+          const unsigned char *row = vt16 + (db * 32 + ql) * kVRow + kofs;
+          const f16x4 v0 = *reinterpret_cast<const f16x4 *>(row);
+          const f16x4 v1 = *reinterpret_cast<const f16x4 *>(row + 16);
+          const f16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[db], 0, 0, 0);
+        }
+      }
+  };
+
+  // ---- the sink tokens: one prefix tile, fp16 as stored (keys past n_sink are zero and masked)
+  if (with_sinks) {
+    for (int i = tid; i < kKV * kD; i += kThreads) {
+      const int j = i & 63, d = i >> 6;
+      f16 kv = (f16)0.f, vv = (f16)0.f;
+      if (j < a.n_sink) {
+        kv = a.k_sink[((int64_t)hk * kD + d) * a.n_sink + j];
+        vv = a.v_sink[((int64_t)hk * a.n_sink + j) * kD + d];
+      }
+      *reinterpret_cast<f16 *>(k16 + j * kKRow + (((d >> 3) ^ (j & 15)) << 4) + (d & 7) * 2) = kv;
+      *reinterpret_cast<f16 *>(vt16 + d * kVRow + j * 2) = vv;
+    }
+    __syncthreads();
+    attend_tile(true, 0);
+  }
+
+  // ---- staging roles: column skey of the tile, waves 0-3 K channel group g, waves 4-7 V channel group g
+  const int skey = tid & 63;
+  const bool is_k = wave < 4;
+  const int g = wave & 3;
+  const int32_t *mat = is_k ? a.kmat : a.vmat;
+  for (int t = t_beg; t < t_end; t++) {
+    const int64_t t0 = (int64_t)t * kKV;
+    const int64_t col = t0 + skey;
+    const bool valid = col < Lc;
+    const int64_t colc = valid ? col : Lc - 1;
+    // P0: the tile's V codebook rows -> LDS; this thread's packed words -> registers
+    for (int i = tid; i < kKV * N; i += kThreads) {
+      const int kk = i / N, c = i % N;
+      const int64_t cc = (t0 + kk < Lc) ? t0 + kk : Lc - 1;
+      vrow[kk * (N + 1) + c] = a.vrows[cc * N + c];
+    }
+    uint32_t w[BITS];
+#pragma unroll
+    for (int i = 0; i < BITS; i++) w[i] = (uint32_t)mat[((int64_t)hk * WPH + g * BITS + i) * ml + colc];
+    __syncthreads();
+    // P1: codes -> fp32 stage (K: the head's per-channel codebook; V: the column's own row)
+    {
+      float *st = (is_k ? kst : vst) + skey * kSR + g * 32;
+      const float *tab = is_k ? klut + g * 32 * N : vrow + skey * (N + 1);
+      const int cstride = is_k ? N : 0;
+      float x[32];
+      static_for<0, 32>([&](auto I) __attribute__((always_inline)) {
+        constexpr int i = decltype(I)::value;
+        x[i] = tab[i * cstride + (int)code_of<BITS, i>(w)];
+      });
+#pragma unroll
+      for (int i = 0; i < 8; i++)
+        *reinterpret_cast<f32x4 *>(st + 4 * i) = f32x4{x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
+    }
+    __syncthreads();
+    // P2: this KV head's outlier residuals (slots g, g + 4, ... of the column)
+    if (valid) {
+      const int base = hk * kD;
+      if (is_k) {
+        for (int s = g; s < a.n_out; s += 4) {
+          const int ch = a.kidx_t[(int64_t)s * ml + col] - base;
+          const float val = a.kout_t[(int64_t)s * ml + col];
+          if ((unsigned)ch < (unsigned)kD && val != 0.f) atomicAdd(&kst[skey * kSR + ch], val);
+        }
+      } else {
+        for (int s = g; s < a.n_out; s += 4) {
+          const int ch = a.vidx[col * a.n_out + s] - base;
+          const float val = a.vout[col * a.n_out + s];
+          if ((unsigned)ch < (unsigned)kD && val != 0.f) atomicAdd(&vst[skey * kSR + ch], val);
+        }
+      }
+    }
+    __syncthreads();
+    // P3: K: RoPE of pairs (j, j + 64), j = 16g .. 16g+15, at position pos_offset + column -> fp16 K tile;
+    //     V: channels 32g .. 32g+31 -> fp16 V^T tile
+    if (is_k) {
+      const float posf = (float)((int)colc + a.pos_offset);
+      const float *kr = kst + skey * kSR;
+      float lo[16], hv[16];
+#pragma unroll
+      for (int i = 0; i < 16; i++) {
+        const int j = 16 * g + i;
+        float sn, cs;
+        sincos_rev(theta[j] * posf, sn, cs);
+        const float klo = kr[j], khi = kr[j + 64];
+        lo[i] = fmaf(cs, klo, -(sn * khi));
+        hv[i] = fmaf(sn, klo, cs * khi);
+      }
+#pragma unroll
+      for (int c = 0; c < 2; c++) {
+        const u32x4 wl = {pack_f16(lo[8 * c], lo[8 * c + 1]), pack_f16(lo[8 * c + 2], lo[8 * c + 3]),
+                          pack_f16(lo[8 * c + 4], lo[8 * c + 5]), pack_f16(lo[8 * c + 6], lo[8 * c + 7])};
+        const u32x4 wh = {pack_f16(hv[8 * c], hv[8 * c + 1]), pack_f16(hv[8 * c + 2], hv[8 * c + 3]),
+                          pack_f16(hv[8 * c + 4], hv[8 * c + 5]), pack_f16(hv[8 * c + 6], hv[8 * c + 7])};
+        const int clo = 2 * g + c, chi = 8 + 2 * g + c;
+        *reinterpret_cast<u32x4 *>(k16 + skey * kKRow + ((clo ^ (skey & 15)) << 4)) = wl;
+        *reinterpret_cast<u32x4 *>(k16 + skey * kKRow + ((chi ^ (skey & 15)) << 4)) = wh;
+      }
+    } else {
+      const float *vr = vst + skey * kSR + g * 32;
+#pragma unroll
+      for (int i = 0; i < 32; i++)
+        *reinterpret_cast<f16 *>(vt16 + (g * 32 + i) * kVRow + skey * 2) = (f16)vr[i];
+    }
+    __syncthreads();
+    attend_tile(false, t0);
+  }
+
+  // ---- partials of this split: unnormalised O^T rows, (max in raw score units, sum)
+  if (qrow < a.S) {
+    const int64_t prow = ((int64_t)h * a.nsplit + split) * a.S + qrow;
+    float *op = a.part_o + prow * kD;
+#pragma unroll
+    for (int db = 0; db < 4; db++)
+#pragma unroll
+      for (int gg = 0; gg < 4; gg++) {
+        const int d = db * 32 + 8 * gg + 4 * hi;
+        *reinterpret_cast<f32x4 *>(op + d) =
+            f32x4{oacc[db][4 * gg], oacc[db][4 * gg + 1], oacc[db][4 * gg + 2], oacc[db][4 * gg + 3]};
+      }
+    if (hi == 0) {
+      a.part_ml[prow * 2] = m_run;
+      a.part_ml[prow * 2 + 1] = l_run;
+    }
+  }
+}
+
+// out[s][h][:] = sum_split w * O_split / sum_split w * l_split, w = 2^((m_split - M) * c), splits in index order
+__global__ __launch_bounds__(kD) void chunk_attn_merge_kernel(const float *__restrict__ part_o,
+                                                              const float *__restrict__ part_ml, float *__restrict__ out,
+                                                              int Hq, int S, int nsplit, float scale_log2e) {
+  const int row = blockIdx.x;              // s * Hq + h
+  const int s = row / Hq, h = row % Hq, d = threadIdx.x;
+  const int64_t base = (int64_t)h * nsplit * S + s;
+  float M = -INFINITY;
+  for (int i = 0; i < nsplit; i++) M = fmaxf(M, part_ml[(base + (int64_t)i * S) * 2]);
+  float l = 0.f, o = 0.f;
+  for (int i = 0; i < nsplit; i++) {
+    const int64_t pr = base + (int64_t)i * S;
+    const float m = part_ml[pr * 2];
+    if (m == -INFINITY) continue;
+    const float w = __builtin_amdgcn_exp2f((m - M) * scale_log2e);
+    l = fmaf(w, part_ml[pr * 2 + 1], l);
+    o = fmaf(w, part_o[pr * kD + d], o);
+  }
+  out[(int64_t)row * kD + d] = l > 0.f ? o / l : 0.f;
+}
+
+struct Plan {
+  int nqb, nsplit, tps;
+  size_t o_bytes, ml_bytes;
+};
+
+static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p) {
+  if (Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 8 || (int64_t)Hkv * kD > 8192 || S <= 0 || S > kMaxS || c0 < 0 ||
+      c0 + S >= (int64_t(1) << 31))
+    return false;
+  p.nqb = (S + kQW - 1) / kQW;
+  const int64_t tiles = (c0 + S + kKV - 1) / kKV;
+  const int64_t base = (int64_t)Hq * p.nqb;
+  int64_t ns = (kTargetWorkgroups + base - 1) / base;
+  const int64_t cap = tiles / kMinTilesPerSplit > 1 ? tiles / kMinTilesPerSplit : 1;
+  if (ns > cap) ns = cap;
+  if (ns > kMaxSplits) ns = kMaxSplits;
+  if (ns < 1) ns = 1;
+  auto bytes = [&](int64_t n) { return align256((size_t)Hq * n * S * kD * 4) + align256((size_t)Hq * n * S * 8); };
+  while (ns > 1 && bytes(ns) > kMaxWorkspace) ns--;
+  p.tps = (int)((tiles + ns - 1) / ns);
+  p.nsplit = (int)((tiles + p.tps - 1) / p.tps);
+  p.o_bytes = align256((size_t)Hq * p.nsplit * S * kD * 4);
+  p.ml_bytes = align256((size_t)Hq * p.nsplit * S * 8);
+  return true;
+}
+
+}  // namespace chunk
+}  // namespace kvq
+
+using namespace kvq;
+
+extern "C" {
+
+size_t kvq_chunk_attention_workspace_bytes(int Hq, int Hkv, int S, int64_t c0) {
+  chunk::Plan p;
+  if (!chunk::plan(Hq, Hkv, S, c0, p)) return 0;
+  return p.o_bytes + p.ml_bytes;
+}
+
+int kvq_chunk_attention(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                        int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  if (!ly || !q || !out) return KVQ_EINVAL;
+  const int bits = ly->bits;
+  if ((bits != 2 && bits != 3 && bits != 4) || ly->hd != chunk::kD || ly->thr_k <= 0) return KVQ_EINVAL;
+  chunk::Plan p;
+  if (!chunk::plan(Hq, ly->H, S, c0, p)) return KVQ_EINVAL;
+  if (ly->max_len <= 0 || ly->max_len >= (int64_t(1) << 31) || c0 + S > ly->max_len || ly->pos_offset < 0 ||
+      c0 + S + ly->pos_offset >= (int64_t(1) << 31))
+    return KVQ_EINVAL;
+  const float *klut = ly->klut_score ? ly->klut_score : ly->klut;
+  const float *vrows = ly->v_mix_rows ? ly->v_mix_rows : ly->vlut_rows;
+  if (!ly->kmat || !ly->vmat || !klut || !vrows || !ly->koutliers_t || !ly->kidx_t || !ly->voutliers || !ly->vidx)
+    return KVQ_EINVAL;
+  if (n_sink < 0 || n_sink > chunk::kMaxSink || (n_sink > 0 && (!k_sink || !v_sink))) return KVQ_EINVAL;
+  // q rows are read as 16-byte vectors, partials / output as 16-byte vectors
+  if ((q_stride_h | q_stride_s) % 8 || q_stride_h < 0 || q_stride_s < 0 || reinterpret_cast<uintptr_t>(q) % 16 ||
+      reinterpret_cast<uintptr_t>(out) % 16 || (k_sink && reinterpret_cast<uintptr_t>(k_sink) % 2) ||
+      (v_sink && reinterpret_cast<uintptr_t>(v_sink) % 2))
+    return KVQ_EINVAL;
+  if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < p.o_bytes + p.ml_bytes)
+    return KVQ_EWORKSPACE;
+  chunk::Args a;
+  a.kmat = ly->kmat;
+  a.vmat = ly->vmat;
+  a.klut = klut;
+  a.kout_t = ly->koutliers_t;
+  a.kidx_t = ly->kidx_t;
+  a.vrows = vrows;
+  a.vout = ly->voutliers;
+  a.vidx = ly->vidx;
+  a.q = reinterpret_cast<const chunk::f16 *>(q);
+  a.qsh = q_stride_h;
+  a.qss = q_stride_s;
+  a.k_sink = reinterpret_cast<const chunk::f16 *>(k_sink);
+  a.v_sink = reinterpret_cast<const chunk::f16 *>(v_sink);
+  a.part_o = reinterpret_cast<float *>(workspace);
+  a.part_ml = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + p.o_bytes);
+  a.max_len = ly->max_len;
+  a.c0 = c0;
+  a.Hq = Hq;
+  a.G = Hq / ly->H;
+  a.S = S;
+  a.n_sink = n_sink;
+  a.n_out = 2 * ly->thr_k;
+  a.pos_offset = ly->pos_offset;
+  a.nqb = p.nqb;
+  a.nsplit = p.nsplit;
+  a.tps = p.tps;
+  a.rope_theta = ly->rope_theta;
+  a.scale_log2e = (1.0f / sqrtf((float)chunk::kD)) * 1.4426950408889634f;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)((int64_t)Hq * p.nqb * p.nsplit)), block(chunk::kThreads);
+  if (bits == 4) chunk::chunk_attn_kernel<4><<<grid, block, 0, st>>>(a);
+  else if (bits == 3) chunk::chunk_attn_kernel<3><<<grid, block, 0, st>>>(a);
+  else chunk::chunk_attn_kernel<2><<<grid, block, 0, st>>>(a);
+  int rc = check_launch();
+  if (rc) return rc;
+  chunk::chunk_attn_merge_kernel<<<(unsigned)((int64_t)S * Hq), chunk::kD, 0, st>>>(a.part_o, a.part_ml, out, Hq, S,
+                                                                                     p.nsplit, a.scale_log2e);
+  return check_launch();
+}
+
+}  // extern "C"

@@ -328,7 +328,12 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
     prompt with the generated tokens appended, and the loop stops at `max_length` positions (:2401-2406) or once EOS
     has been produced.  Greedy by default; `do_sample=True` is what lwm/llama_inference.py:124-131 asks for
     (multinomial sampling after HF's default warpers: temperature 1, top-k 50; `min_length` suppresses EOS until the
-    sequence is that long).  Batch 1."""
+    sequence is that long).  Batch 1.
+    The caches are NOT reset: on a model whose caches are warm (an earlier generate() or forward) `input_ids` continues
+    the conversation -- its positions follow the caches' length, and the whole follow-up prompt goes through the
+    attention as one chunk over the compressed cache (KVQuantAttention.attend_multi -> cache.chunk_kv).  The returned
+    sequence is `input_ids` with the new tokens appended (the earlier turns are in the caches, not in it).  Reset with
+    load_quantizers() or each layer's kvq.reset() to start a new conversation."""
     if input_ids.shape[0] != 1:
         raise ValueError("the compressed-cache path is batch 1 (ML:1408)")
     dev = model.gpus[0] if hasattr(model, "gpus") else next(model.parameters()).device

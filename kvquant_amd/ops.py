@@ -839,3 +839,33 @@ def prefill_attention_gqa(q, k, v, softmax_scale=None):
                                                  v.stride(1), out.stride(1), out.stride(0), scale, _stream()),
                    "kvq_prefill_attention_gqa")
     return out.view(S, Hq * hd)
+
+
+# ---- a chunk of S new tokens over the compressed cache (MFMA flash kernel, kvq_chunk_attn.hip) ---------------------
+def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None):
+    """kvq_chunk_attention: query i of q (fp16 [Hq, S, 128] view, contiguous last dimension; RoPE'd at position
+    pos_offset + c0 + i) over the fp16 sink tokens and the compressed columns [0, c0 + i] of the layer (struct from
+    make_layer, layer.H = KV heads; the chunk must already be packed into columns c0 .. c0+S-1).  k_sink fp16
+    [Hkv, 128, n_sink] (post-RoPE) / v_sink fp16 [Hkv, n_sink, 128], or None.  Returns out f32 [S, Hq, 128]."""
+    if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float16 and q.dim() == 3 and q.stride(2) == 1):
+        raise ValueError("q: expected an fp16 GPU tensor [Hq, S, 128] with a contiguous last dimension")
+    if q.shape[0] != Hq or q.shape[2] != 128:
+        raise ValueError("q: expected [%d, S, 128], got %s" % (Hq, tuple(q.shape)))
+    if (k_sink is None) != (v_sink is None):
+        raise ValueError("k_sink and v_sink come together")
+    S = q.shape[1]
+    n_sink = 0 if k_sink is None else int(k_sink.shape[2])
+    if out is None:
+        out = torch.empty((S, Hq, 128), dtype=torch.float32, device=q.device)
+    with _Dev(out):
+        nbytes = _L().kvq_chunk_attention_workspace_bytes(int(Hq), layer.H, int(S), int(c0))
+        if nbytes == 0:
+            raise ValueError("chunk_attention: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
+        ws = _workspace(out.device, nbytes + 256, slot="chunk")
+        base = (ws.data_ptr() + 255) & ~255
+        _lib.check(_L().kvq_chunk_attention(
+            ctypes.byref(layer), int(Hq), int(S), int(c0), q.data_ptr(), q.stride(0), q.stride(1),
+            None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
+            base, ws.numel() - (base - ws.data_ptr()), _stream()), "kvq_chunk_attention")
+    return out
