@@ -75,6 +75,10 @@ extern "C" {
  *        existing entry point, struct and behaviour is unchanged.
  *        Later in 403: kvq_chunk_attention[_workspace_bytes] (attention of a multi-token chunk over the compressed
  *        cache).  Additive only, so kvq_version() stays 403: a caller that needs them looks the symbols up.
+ *        Later in 403: scaled RoPE (struct kvq_rope; kvq_score_k_rope, kvq_score_k_prepared_rope,
+ *        kvq_score_k_prepared_softmax_rope, kvq_score_k_gqa_rope, kvq_decode_step_rope, kvq_decode_step_gqa_rope,
+ *        kvq_chunk_attention_rope): the K rotation takes an explicit frequency table and attention factor.  Each existing
+ *        entry is its _rope twin with rope = NULL; kvq_layer is unchanged.  Additive only, kvq_version() stays 403.
  *        A binding checks `kvq_version() / 100 == KVQ_ABI_MAJOR`. */
 #define KVQ_ABI_MAJOR 4
 KVQ_API int kvq_version(void);
@@ -608,6 +612,54 @@ KVQ_API size_t kvq_chunk_attention_workspace_bytes(int Hq, int Hkv, int S, int64
 KVQ_API int kvq_chunk_attention(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
                                 int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- scaled RoPE (ABI 403): an explicit frequency table for the K rotation ------------------------------------------
+ * Every kernel above rotates the dequantised pre-RoPE keys at angle fl32(theta_j * pos) with theta_j =
+ * powf(rope_theta, -2j/128) evaluated on the device.  Models with scaled RoPE (transformers' rope types linear, dynamic,
+ * yarn, llama3) rotate with other frequencies and may scale cos / sin by an attention factor.  The _rope twins below take
+ *   inv_freq: device f32 [64], the frequencies theta_j themselves (transformers' rotary_emb.inv_freq), finite and > 0;
+ *   attention_factor: finite and > 0 (1 for every type but yarn);
+ * and rotate at fl32(inv_freq[j] * pos) with (cos, sin) multiplied by attention_factor -- the COMPRESSED columns only:
+ * fp16 sink keys and the query are rotated by the caller with the scaled rows and already carry the factor.  rope =
+ * NULL is the theta rule above, i.e. the existing entry point (same kernels, same bits).  The table is read on the
+ * device; the host checks the pointer (non-NULL, 4-byte aligned) and the factor before any launch, the table's values
+ * are the caller's to check (kvquant_amd.rope does).  The table must stay valid until the launches have completed. */
+typedef struct kvq_rope {
+  const float *inv_freq;      /* device f32 [64] */
+  float attention_factor;
+} kvq_rope;
+KVQ_API int kvq_score_k_rope(int bits, const float *q, const int32_t *mat, float *mul, const float *lut, int q_len, int H,
+                             int hd, int64_t L, int64_t max_len, float rope_theta, int pos_offset, const float *outliers,
+                             const int32_t *outlier_idx, int n_out, int accumulate, void *workspace,
+                             size_t workspace_bytes, const kvq_rope *rope, void *stream);
+KVQ_API int kvq_score_k_prepared_rope(int bits, const int32_t *mat, float *mul, const float *lut, int H, int hd, int64_t L,
+                                      int64_t max_len, float rope_theta, int pos_offset, const float *outliers,
+                                      const int32_t *outlier_idx, int n_out, int accumulate, void *workspace,
+                                      size_t workspace_bytes, const kvq_rope *rope, void *stream);
+KVQ_API int kvq_score_k_prepared_softmax_rope(int bits, const int32_t *mat, float *mul, const float *lut, int H, int hd,
+                                              int64_t L, int64_t max_len, float rope_theta, int pos_offset,
+                                              const float *outliers, const int32_t *outlier_idx, int n_out,
+                                              const float *outliers_t, const int32_t *outlier_idx_t, void *workspace,
+                                              size_t workspace_bytes, float inv_sqrt_hd, float *softmax_parts,
+                                              int n_parts, int flags, const kvq_rope *rope, void *stream);
+KVQ_API int kvq_score_k_gqa_rope(int bits, const void *q, int q_is_half, const int32_t *mat, float *mul, const float *lut,
+                                 int Hq, int Hkv, int hd, int64_t L, int64_t max_len, float rope_theta, int pos_offset,
+                                 const float *outliers_t, const int32_t *outlier_idx_t, int n_out, float inv_sqrt_hd,
+                                 float *softmax_parts, int n_parts, void *workspace, size_t workspace_bytes,
+                                 const kvq_rope *rope, void *stream);
+/* (with a table, fuse_softmax = 3 runs as 1: kvq_fused_attend keeps the theta rule) */
+KVQ_API int kvq_decode_step_rope(const kvq_layer *layer, int64_t kcol, int64_t vcol, const void *q, const void *k,
+                                 const void *v, int acts_are_half, const kvq_sinks *sinks, const uint16_t *v_sink,
+                                 uint16_t *sink_probs, float *out, int fuse_softmax, void *workspace,
+                                 size_t workspace_bytes, const kvq_rope *rope, void *stream);
+KVQ_API int kvq_decode_step_gqa_rope(const kvq_layer *layer, int Hq, int64_t col, const void *q, const void *k,
+                                     const void *v, int acts_are_half, const uint16_t *sink_scores, int n_sink,
+                                     const uint16_t *v_sink, uint16_t *sink_probs, float *out, void *workspace,
+                                     size_t workspace_bytes, const kvq_rope *rope, void *stream);
+KVQ_API int kvq_chunk_attention_rope(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q,
+                                     int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                     const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                     size_t workspace_bytes, const kvq_rope *rope, void *stream);
 
 /* ---- uncapped ("orig") Dense-and-Sparse variants, 4 bit only ------------------ */
 

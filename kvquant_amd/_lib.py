@@ -45,6 +45,14 @@ class Layer(ctypes.Structure):
 
 _ly = ctypes.POINTER(Layer)
 
+
+class Rope(ctypes.Structure):
+    """struct kvq_rope of include/kvq.h"""
+    _fields_ = [("inv_freq", ctypes.c_void_p), ("attention_factor", ctypes.c_float)]
+
+
+_rp = ctypes.POINTER(Rope)
+
 # name -> (restype, argtypes); mirrors include/kvq.h one to one
 SIGNATURES = {
     "kvq_version": (_i, []),
@@ -113,6 +121,15 @@ SIGNATURES = {
                                        _f, _vp]),
     "kvq_chunk_attention_workspace_bytes": (_sz, [_i, _i, _i, _i64]),
     "kvq_chunk_attention": (_i, [_ly, _i, _i, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "kvq_score_k_rope": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _f, _i, _vp, _vp, _i, _i, _vp, _sz, _rp, _vp]),
+    "kvq_score_k_prepared_rope": (_i, [_i, _vp, _vp, _vp, _i, _i, _i64, _i64, _f, _i, _vp, _vp, _i, _i, _vp, _sz, _rp, _vp]),
+    "kvq_score_k_prepared_softmax_rope": (_i, [_i, _vp, _vp, _vp, _i, _i, _i64, _i64, _f, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                                               _sz, _f, _vp, _i, _i, _rp, _vp]),
+    "kvq_score_k_gqa_rope": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _f, _i, _vp, _vp, _i, _f, _vp, _i, _vp,
+                                  _sz, _rp, _vp]),
+    "kvq_decode_step_rope": (_i, [_ly, _i64, _i64, _vp, _vp, _vp, _i, _sk, _vp, _vp, _vp, _i, _vp, _sz, _rp, _vp]),
+    "kvq_decode_step_gqa_rope": (_i, [_ly, _i, _i64, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _rp, _vp]),
+    "kvq_chunk_attention_rope": (_i, [_ly, _i, _i, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _sz, _rp, _vp]),
     "kvq_append_k_sparse_orig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "kvq_append_v_sparse_orig": (_i, [_vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "kvq_spmv_k_rope_csr": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _f, _i, _vp]),

@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from . import rope as rope_mod
 from .cache import QuantK, QuantV, chunk_kv, decode_kv
 
 # q_len > 1 on a warm cache (multi-turn prompts, draft verification, chunked fills) takes kvq_chunk_attention
@@ -50,13 +51,25 @@ def rotate_half(x):
 
 class RotaryDynamic(nn.Module):
     """LlamaRotaryEmbeddingDynamic (ML:159-177): cos/sin for positions
-    [start, end) computed on the fly, in the activation dtype."""
+    [start, end) computed on the fly, in the activation dtype.
+    rope (kvquant_amd.rope.RopeSpec, optional): scaled RoPE -- the frequencies of transformers' table and the rows
+    (emb.cos() * af).to(dtype), (emb.sin() * af).to(dtype) as LlamaRotaryEmbedding forms them; dynamic NTK takes the
+    table of seq_len = end.  None or a default spec: the theta rule above, unchanged."""
 
-    def __init__(self, dim, base=10000.0, device=None):
+    def __init__(self, dim, base=10000.0, device=None, rope=None):
         super().__init__()
-        inv_freq = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.int64).float().to(device) / dim))
+        self.rope = None if rope is None or rope.is_default else rope
+        if self.rope is not None and not self.rope.dynamic:
+            inv_freq, self.af = self.rope.table(None)
+            inv_freq = inv_freq.to(device)
+        else:
+            inv_freq = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.int64).float().to(device) / dim))
+            self.af = 1.0
         self.register_buffer("inv_freq", inv_freq, persistent=False)
         self.dim, self.base = dim, float(base)
+        # (the cache key of a scaled table: its parameters, so that layers with the same RoPE share the rows)
+        self._rope_key = None if self.rope is None else (self.rope.rope_type, repr(sorted(self.rope.params.items())),
+                                                         self.rope.max_position_embeddings)
 
     # The tables of the last positions asked for, per frequency table / device / dtype: every layer of a model asks for
     # the SAME positions one after the other, and at decode the seven small launches below were a sizeable share of a
@@ -64,8 +77,14 @@ class RotaryDynamic(nn.Module):
     _last = {}
 
     def forward(self, x, start_pos, end_pos):
-        inv = self.inv_freq
+        inv, af = self.inv_freq, self.af
         key = (self.dim, self.base, inv.dtype, inv.device, x.dtype)
+        if self.rope is not None:
+            if self.rope.dynamic:
+                inv, af = self.rope.table(x.device, end_pos)
+                key = key + (self._rope_key, max(int(end_pos), self.rope.max_position_embeddings))
+            else:
+                key = key + (self._rope_key,)
         # (only decode-size requests are kept -- a prefill's [S, dim] tables would be pinned until the next call, 512 MB
         #  after a 1M-token prompt -- and per CUDA stream: the cached tensors were produced on that stream)
         small = end_pos - start_pos <= RotaryDynamic.CACHE_MAX_POSITIONS
@@ -77,7 +96,10 @@ class RotaryDynamic(nn.Module):
         t = torch.arange(start_pos, end_pos, device=x.device, dtype=torch.int64).type_as(inv)
         freqs = torch.outer(t, inv)
         emb = torch.cat((freqs, freqs), dim=-1)
-        cos, sin = emb.cos().to(x.dtype), emb.sin().to(x.dtype)
+        if self.rope is None:
+            cos, sin = emb.cos().to(x.dtype), emb.sin().to(x.dtype)
+        else:      # (LlamaRotaryEmbedding.forward: scaled in fp32, then rounded to the activation dtype)
+            cos, sin = (emb.cos() * af).to(x.dtype), (emb.sin() * af).to(x.dtype)
         if small:
             RotaryDynamic._last[key] = ((start_pos, end_pos), cos, sin)
         return cos, sin
@@ -108,8 +130,13 @@ class KVQuantAttention(nn.Module):
     def __init__(self, hidden_size=4096, num_heads=32, abits=4, include_sparse=True, first_few_fp16=0,
                  maxseqlen=4096, rope_theta=10000.0, sparsity_threshold=0.99, device=None,
                  dtype=torch.float16, bias=False, make_proj=True, use_orig_sparse=False, compact=False,
-                 num_key_value_heads=None):
+                 num_key_value_heads=None, rope_scaling=None, max_position_embeddings=None):
         super().__init__()
+        # scaled RoPE: rope_scaling = a transformers rope_scaling / rope_parameters dict or a kvquant_amd.rope.RopeSpec
+        # (max_position_embeddings: the model's, which dynamic NTK scales from); None = default RoPE (theta rule)
+        self.rope = rope_mod.spec_of(rope_theta, rope_scaling, max_position_embeddings)
+        if use_orig_sparse:
+            rope_mod.require_default(self.rope, "use_orig_sparse (the uncapped CSR kernels)")
         self.hidden_size = hidden_size
         self.num_heads = num_heads
         self.head_dim = hidden_size // num_heads
@@ -131,11 +158,11 @@ class KVQuantAttention(nn.Module):
             self.k_proj = nn.Linear(hidden_size, kv_hidden, bias=bias, **kw)
             self.v_proj = nn.Linear(hidden_size, kv_hidden, bias=bias, **kw)
             self.o_proj = nn.Linear(hidden_size, hidden_size, bias=bias, **kw)
-        self.rotary_emb = RotaryDynamic(self.head_dim, base=rope_theta, device=device)
+        self.rotary_emb = RotaryDynamic(self.head_dim, base=rope_theta, device=device, rope=self.rope)
         self.kcache = QuantK(bits=abits, hidden_size=kv_hidden, num_heads=self.num_key_value_heads,
                              max_position_embeddings=maxseqlen, include_sparse=include_sparse,
                              sparsity_threshold=sparsity_threshold, rope_theta=rope_theta,
-                             first_few_fp16=first_few_fp16, device=device, compact=compact)
+                             first_few_fp16=first_few_fp16, device=device, compact=compact, rope_scaling=self.rope)
         self.vcache = QuantV(bits=abits, hidden_size=kv_hidden, num_heads=self.num_key_value_heads,
                              max_position_embeddings=maxseqlen, include_sparse=include_sparse,
                              sparsity_threshold=sparsity_threshold, first_few_fp16=first_few_fp16,

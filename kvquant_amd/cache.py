@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from . import rope as rope_mod
 
 ZERO_CODE = {4: 7, 3: 3, 2: 1}  # KCU:2084 / 2442 / 3020
 
@@ -57,10 +58,17 @@ class QuantK(nn.Module):
 
     def __init__(self, bits=2, hidden_size=4096, num_heads=32, max_position_embeddings=-1,
                  include_sparse=False, sparsity_threshold=0.99, rope_theta=10000, use_orig_sparse=False,
-                 first_few_fp16=0, device=None, compact=False, outlier_width=None):
+                 first_few_fp16=0, device=None, compact=False, outlier_width=None, rope_scaling=None):
         super().__init__()
         if bits not in (2, 3, 4):
             raise ValueError("bits must be 2, 3 or 4")
+        # scaled RoPE (kvquant_amd.rope): None / a rope_scaling dict / a RopeSpec; default RoPE keeps the theta rule
+        self.rope = rope_mod.spec_of(rope_theta, rope_scaling)
+        if use_orig_sparse:
+            rope_mod.require_default(self.rope, "use_orig_sparse (the uncapped CSR kernels)")
+        if self.rope.dynamic and first_few_fp16 > 0:
+            raise ValueError("scaled RoPE (dynamic) with first_few_fp16 > 0: the fp16 sink keys are stored post-RoPE and "
+                             "would keep the angles of the table they were written with")
         if compact and not include_sparse:
             raise ValueError("compact is a format of the Dense-and-Sparse cache (include_sparse)")
         if use_orig_sparse and bits != 4:
@@ -131,6 +139,13 @@ class QuantK(nn.Module):
     @property
     def device(self):
         return self.kcache.device
+
+    def rope_table(self, seq_len):
+        """the (inv_freq, attention factor) the kernels rotate this cache's keys with when the call's last position is
+        seq_len - 1 (kvquant_amd.rope), or None for default RoPE (the theta rule)"""
+        if self.rope.is_default:
+            return None
+        return self.rope.table(self.device, seq_len)
 
     def _reset_csr(self, dev):
         # uncapped-outlier CSR state (ML:402-408)
@@ -213,6 +228,7 @@ class QuantK(nn.Module):
         if self.compact:
             raise NotImplementedError("compact caches are read by decode_kv only (the reference-format kernels need the rows)")
         pos = self.klen - self.first_few_fp16
+        rope = self.rope_table(self.klen + 1)
         if self.include_sparse:
             lut_off = self.lookup_table2 if self.norm else self.lookup_table
             ops.append_k_fused(self.bits, self.kcache, self.lookup_table, lut_off, k,
@@ -227,10 +243,10 @@ class QuantK(nn.Module):
         table = self.lookup_table2 if (self.norm and self.bits == 2) else self.lookup_table  # ML:811-815
         if self.include_sparse:
             ops.score_k(self.bits, q, self.kcache, mul, table, L, self.rope_theta, self.first_few_fp16,
-                        self.outliers, self.outlier_indices, accumulate=False)
+                        self.outliers, self.outlier_indices, accumulate=False, rope=rope)
         else:
             ops.score_k(self.bits, q, self.kcache, mul, table, L, self.rope_theta, self.first_few_fp16,
-                        accumulate=False)
+                        accumulate=False, rope=rope)
         return mul
 
     def forward_fused_sparse(self, q, k):
@@ -605,6 +621,7 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     bits = kc.bits
     kpos = kc.klen - kc.first_few_fp16
     vpos = vc.vlen - vc.first_few_fp16
+    rope = kc.rope_table(kc.klen + 1)      # (scaled RoPE: the table of this step's position; None: the theta rule)
     lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
     # the score tables are built from the table the reference dequantises with: the Q-Norm one at 2 bit (ML:811-815)
     table = kc.lookup_table2 if (kc.norm and bits == 2) else kc.lookup_table
@@ -634,7 +651,10 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
         fuse = FUSE_SOFTMAX_INTO_MIX_V or L <= FUSE_SOFTMAX_UP_TO
         fused = FUSED_ATTEND if FUSED_ATTEND is not None else (bits == 4 and L >= FUSED_ATTEND_FROM)
         mode = (3 if fused else 1) if fuse else 0
-        ops.decode_step(cached[1], kpos, q, k, v, out, mode, sinks, v_sink, sink_probs)
+        if rope is None:
+            ops.decode_step(cached[1], kpos, q, k, v, out, mode, sinks, v_sink, sink_probs)
+        else:
+            ops.decode_step(cached[1], kpos, q, k, v, out, mode, sinks, v_sink, sink_probs, rope=rope)
         kc.klen += 1
         vc.vlen += 1
         return out, sink_probs
@@ -652,11 +672,12 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
         sink_probs = ops.score_k_mix_v(bits, kc.kcache, scores, table, L, kc.rope_theta, kc.first_few_fp16, ws,
                                        kc.outliers, kc.outlier_indices, inv, vc.vcache, out,
                                        vc.mix_table(), vc.outliers, vc.outlier_indices, sink_scores, kc.outliers_t,
-                                       kc.outlier_indices_t, v_sink, f16_pair=kc.bits == 3 and kc.score_f16_pair)
+                                       kc.outlier_indices_t, v_sink, f16_pair=kc.bits == 3 and kc.score_f16_pair,
+                                       rope=rope)
         return out, sink_probs
     probs, sink_probs = ops.score_k_softmax(bits, kc.kcache, scores, table, L, kc.rope_theta, kc.first_few_fp16, ws,
                                             kc.outliers, kc.outlier_indices, inv, sink_scores,
-                                            kc.outliers_t, kc.outlier_indices_t, v_sink, out)
+                                            kc.outliers_t, kc.outlier_indices_t, v_sink, out, rope=rope)
     ops.mix_v(bits, probs.unsqueeze(0), vc.vcache, out, vc.mix_table(), L, vc.outliers, vc.outlier_indices,
               accumulate=v_sink is not None)
     return out, sink_probs
@@ -687,6 +708,7 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     vpos = vc.vlen - vc.first_few_fp16
     if kpos != vpos:
         raise ValueError("decode_kv (GQA): K and V caches must be in step")
+    rope = kc.rope_table(kc.klen + 1)
     lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
     table = kc.lookup_table2 if (kc.norm and kc.bits == 2) else kc.lookup_table
     inv = 1.0 / (kc.head_dim ** 0.5)
@@ -706,7 +728,7 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
         kc._step_layer = cached
     out = torch.empty((1, Hq, vc.head_dim), dtype=torch.float32, device=kc.device)
     sink_probs = None if sink_scores is None else torch.empty_like(sink_scores)
-    ops.decode_step_gqa(cached[1], Hq, kpos, q, k, v, out, sink_scores, v_rep, sink_probs)
+    ops.decode_step_gqa(cached[1], Hq, kpos, q, k, v, out, sink_scores, v_rep, sink_probs, rope=rope)
     kc.klen += 1
     vc.vlen += 1
     return out, sink_probs
@@ -740,6 +762,7 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
     c0 = kc.klen - sinks
     if c0 + S > kc.max_len:
         raise ValueError("chunk_kv: %d + %d tokens exceed the cache (%d columns)" % (c0, S, kc.max_len))
+    rope = kc.rope_table(kc.klen + S)      # (dynamic: the table of the chunk's last position, for every column)
     kc.parallel_pack(k)
     vc.parallel_pack(v)
     lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
@@ -756,7 +779,7 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
     # (query rows past a piece see only columns up to their own: a later piece is the same call with c0 moved on)
     for s0 in range(0, S, CHUNK_PIECE):
         n = min(CHUNK_PIECE, S - s0)
-        ops.chunk_attention(cached[1], Hq, c0 + s0, q[:, s0:s0 + n], out[s0:s0 + n], ks, vs)
+        ops.chunk_attention(cached[1], Hq, c0 + s0, q[:, s0:s0 + n], out[s0:s0 + n], ks, vs, rope=rope)
     return out
 
 
@@ -783,6 +806,7 @@ def shard_attention(kc, vc, q, k=None, v=None, pos_base=0, record=None, k_sink=N
     (no cached tokens, no new one, no sinks) returns zeros with (M, Z) = (-inf, 0).  Sparse caches with the outlier mirror."""
     if not (kc.include_sparse and vc.include_sparse):
         raise ValueError("shard_attention needs include_sparse caches")
+    rope_mod.require_default(getattr(kc, "rope", None), "shard_attention (the token-sharded path)")
     if q.dim() != 2 or q.shape[0] != kc.num_heads:
         raise ValueError("shard_attention: q must be [%d, 128] -- the token-sharded path is MHA only (no grouped-query "
                          "attention)" % kc.num_heads)
@@ -880,7 +904,8 @@ class HeadShard:
     the tables stay per layer).  Reference outlier format."""
 
     def __init__(self, bits, hidden_size, num_heads, heads, max_position_embeddings, sparsity_threshold=0.99,
-                 rope_theta=10000, device=None, stage_len=64, first_few_fp16=0, staging=None):
+                 rope_theta=10000, device=None, stage_len=64, first_few_fp16=0, staging=None, rope_scaling=None):
+        rope_mod.require_default(rope_mod.spec_of(rope_theta, rope_scaling), "HeadShard (the head-sharded path)")
         h0, n = int(heads[0]), int(heads[1])
         if not (0 <= h0 and n > 0 and h0 + n <= num_heads):
             raise ValueError("HeadShard: heads (%d, %d) outside 0..%d" % (h0, n, num_heads))

@@ -74,17 +74,23 @@ __device__ __forceinline__ uint32_t pack_f16(float a, float b) {
   return r;
 }
 
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
+// RT (scaled RoPE, kvq.h: kvq_rope): the K tiles rotate with the frequencies rt_freq [64] and (cos, sin) scaled by the
+// attention factor rt_af (before the fp16 rounding of the tile); chunk_attn_kernel_rt below
+// (the LDS arrays are the kernels' own, declared by KVQ_CHUNK_LDS)
+#define KVQ_CHUNK_LDS                                                  \
+  __shared__ float klut[kD * (1 << BITS)];                             \
+  __shared__ float theta[64];                                          \
+  __shared__ float vrow[kKV * ((1 << BITS) + 1)];                      \
+  __shared__ __attribute__((aligned(16))) float kst[kKV * kSR];        \
+  __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];        \
+  __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow]; \
+  __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
+template <int BITS, bool RT>
+__device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, float *theta, float *vrow, float *kst,
+                                                float *vst, unsigned char *k16, unsigned char *vt16, const float *rt_freq,
+                                                float rt_af) {
   constexpr int N = 1 << BITS;
   constexpr int WPH = kD / 32 * BITS;
-  __shared__ float klut[kD * N];
-  __shared__ float theta[64];
-  __shared__ float vrow[kKV * (N + 1)];
-  __shared__ __attribute__((aligned(16))) float kst[kKV * kSR];
-  __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];
-  __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow];
-  __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hi = lane >> 5, ql = lane & 31;
@@ -107,7 +113,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
   const bool with_sinks = split == 0 && a.n_sink > 0;
 
   for (int e = tid; e < kD * N; e += kThreads) klut[e] = a.klut[(int64_t)hk * kD * N + e];
-  if (tid < 64) theta[tid] = rope_freq(a.rope_theta, tid);
+  if (tid < 64) theta[tid] = RT ? rt_freq[tid] : rope_freq(a.rope_theta, tid);
 
   // ---- Q fragments (B operand of S^T): lane (q, hi) holds Q[q][ks*16 + hi*8 .. +7]
   f16x8 qf[8];
@@ -280,6 +286,10 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
         const int j = 16 * g + i;
         float sn, cs;
         sincos_rev(theta[j] * posf, sn, cs);
+        if constexpr (RT) {
+          sn *= rt_af;
+          cs *= rt_af;
+        }
         const float klo = kr[j], khi = kr[j + 64];
         lo[i] = fmaf(cs, klo, -(sn * khi));
         hv[i] = fmaf(sn, klo, cs * khi);
@@ -322,6 +332,19 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
     }
   }
 }
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
+  KVQ_CHUNK_LDS
+  chunk_attn_body<BITS, false>(a, klut, theta, vrow, kst, vst, k16, vt16, nullptr, 1.f);
+}
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel_rt(Args a, const float *rt_freq, float rt_af) {
+  KVQ_CHUNK_LDS
+  chunk_attn_body<BITS, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af);
+}
+#undef KVQ_CHUNK_LDS
 
 // out[s][h][:] = sum_split w * O_split / sum_split w * l_split, w = 2^((m_split - M) * c), splits in index order
 __global__ __launch_bounds__(kD) void chunk_attn_merge_kernel(const float *__restrict__ part_o,
@@ -388,7 +411,14 @@ size_t kvq_chunk_attention_workspace_bytes(int Hq, int Hkv, int S, int64_t c0) {
 int kvq_chunk_attention(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
                         int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
                         void *workspace, size_t workspace_bytes, void *stream) {
-  if (!ly || !q || !out) return KVQ_EINVAL;
+  return kvq_chunk_attention_rope(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                  workspace_bytes, nullptr, stream);
+}
+
+int kvq_chunk_attention_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                             int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                             void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream) {
+  if (!ly || !q || !out || !rope_ok(rope)) return KVQ_EINVAL;
   const int bits = ly->bits;
   if ((bits != 2 && bits != 3 && bits != 4) || ly->hd != chunk::kD || ly->thr_k <= 0) return KVQ_EINVAL;
   chunk::Plan p;
@@ -439,9 +469,17 @@ int kvq_chunk_attention(const kvq_layer *ly, int Hq, int S, int64_t c0, const vo
   a.scale_log2e = (1.0f / sqrtf((float)chunk::kD)) * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((int64_t)Hq * p.nqb * p.nsplit)), block(chunk::kThreads);
-  if (bits == 4) chunk::chunk_attn_kernel<4><<<grid, block, 0, st>>>(a);
-  else if (bits == 3) chunk::chunk_attn_kernel<3><<<grid, block, 0, st>>>(a);
-  else chunk::chunk_attn_kernel<2><<<grid, block, 0, st>>>(a);
+  if (rope) {
+    const float *f = rope->inv_freq;
+    const float af = rope->attention_factor;
+    if (bits == 4) chunk::chunk_attn_kernel_rt<4><<<grid, block, 0, st>>>(a, f, af);
+    else if (bits == 3) chunk::chunk_attn_kernel_rt<3><<<grid, block, 0, st>>>(a, f, af);
+    else chunk::chunk_attn_kernel_rt<2><<<grid, block, 0, st>>>(a, f, af);
+  } else {
+    if (bits == 4) chunk::chunk_attn_kernel<4><<<grid, block, 0, st>>>(a);
+    else if (bits == 3) chunk::chunk_attn_kernel<3><<<grid, block, 0, st>>>(a);
+    else chunk::chunk_attn_kernel<2><<<grid, block, 0, st>>>(a);
+  }
   int rc = check_launch();
   if (rc) return rc;
   chunk::chunk_attn_merge_kernel<<<(unsigned)((int64_t)S * Hq), chunk::kD, 0, st>>>(a.part_o, a.part_ml, out, Hq, S,

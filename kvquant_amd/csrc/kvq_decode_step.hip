@@ -132,7 +132,15 @@ size_t kvq_decode_step_workspace_bytes(int bits, int H, int hd, int64_t L) {
 int kvq_decode_step(const kvq_layer *ly, int64_t kcol, int64_t vcol, const void *q, const void *k, const void *v,
                     int acts_are_half, const kvq_sinks *sinks, const uint16_t *v_sink, uint16_t *sink_probs,
                     float *out, int fuse_softmax, void *workspace, size_t workspace_bytes, void *stream) {
-  if (!ly || !q || !k || !v || !out || kcol < 0 || vcol != kcol) return KVQ_EINVAL;
+  return kvq_decode_step_rope(ly, kcol, vcol, q, k, v, acts_are_half, sinks, v_sink, sink_probs, out, fuse_softmax,
+                              workspace, workspace_bytes, nullptr, stream);
+}
+
+int kvq_decode_step_rope(const kvq_layer *ly, int64_t kcol, int64_t vcol, const void *q, const void *k, const void *v,
+                         int acts_are_half, const kvq_sinks *sinks, const uint16_t *v_sink, uint16_t *sink_probs,
+                         float *out, int fuse_softmax, void *workspace, size_t workspace_bytes, const kvq_rope *rope,
+                         void *stream) {
+  if (!ly || !q || !k || !v || !out || kcol < 0 || vcol != kcol || !rope_ok(rope)) return KVQ_EINVAL;
   // Dense-and-Sparse caches with the K mirror; value arrays may be absent (COMPACT formats: packed entries in the index
   // arrays, include/kvq.h)
   if (!ly->kidx_t || !ly->vidx || (ly->koutliers && !ly->kidx) || (ly->koutliers_t && !ly->kidx_t)) return KVQ_EINVAL;
@@ -159,7 +167,8 @@ int kvq_decode_step(const kvq_layer *ly, int64_t kcol, int64_t vcol, const void 
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   struct Clear { ~Clear() { step_events = nullptr; } } clear_events_on_exit;
-  if (fuse_softmax == 3 && ly->koutliers_t && ly->voutliers && !ly->v_mix_rows && !ly->klut_score &&
+  // (the fused kernel rotates with the theta rule only: with a frequency table the step takes the kernel pair)
+  if (fuse_softmax == 3 && !rope && ly->koutliers_t && ly->voutliers && !ly->v_mix_rows && !ly->klut_score &&
       kvq_fused_attend_supported(bits, H, hd, L, ly->max_len, n_out)) {
     // one kernel for q.K^T + softmax + p.V of every 256-token tile, then the merge (events: 0-1 the kernel, 2-3 the merge)
     last_route = 3;
@@ -175,10 +184,10 @@ int kvq_decode_step(const kvq_layer *ly, int64_t kcol, int64_t vcol, const void 
   }
   last_route = fuse_softmax ? 1 : 0;
   record(0, st);
-  rc = kvq_score_k_prepared_softmax_ex(bits, ly->kmat, scores, ktab, H, hd, L, ly->max_len, ly->rope_theta,
-                                       ly->pos_offset, ly->koutliers, ly->kidx, n_out, ly->koutliers_t, ly->kidx_t, ws,
-                                       p.score_ws, inv, parts, p.n_parts,
-                                       score_flags_of(ly, L), stream);
+  rc = kvq_score_k_prepared_softmax_rope(bits, ly->kmat, scores, ktab, H, hd, L, ly->max_len, ly->rope_theta,
+                                         ly->pos_offset, ly->koutliers, ly->kidx, n_out, ly->koutliers_t, ly->kidx_t, ws,
+                                         p.score_ws, inv, parts, p.n_parts,
+                                         score_flags_of(ly, L), rope, stream);
   record(1, st);
   if (rc) return rc;
   return step_tail(ly, sinks, v_sink, sink_probs, out, fuse_softmax, scores, probs, parts, p.n_parts, ws, p, L, n_out, n_sink, inv, st);
@@ -326,8 +335,16 @@ size_t kvq_decode_step_gqa_workspace_bytes(int bits, int Hq, int Hkv, int hd, in
 int kvq_decode_step_gqa(const kvq_layer *ly, int Hq, int64_t col, const void *q, const void *k, const void *v,
                         int acts_are_half, const uint16_t *sink_scores, int n_sink, const uint16_t *v_sink,
                         uint16_t *sink_probs, float *out, void *workspace, size_t workspace_bytes, void *stream) {
+  return kvq_decode_step_gqa_rope(ly, Hq, col, q, k, v, acts_are_half, sink_scores, n_sink, v_sink, sink_probs, out,
+                                  workspace, workspace_bytes, nullptr, stream);
+}
+
+int kvq_decode_step_gqa_rope(const kvq_layer *ly, int Hq, int64_t col, const void *q, const void *k, const void *v,
+                             int acts_are_half, const uint16_t *sink_scores, int n_sink, const uint16_t *v_sink,
+                             uint16_t *sink_probs, float *out, void *workspace, size_t workspace_bytes,
+                             const kvq_rope *rope, void *stream) {
   // every argument is checked before the first launch: a refused call leaves the cache untouched
-  if (!ly || !q || !k || !v || !out || col < 0) return KVQ_EINVAL;
+  if (!ly || !q || !k || !v || !out || col < 0 || !rope_ok(rope)) return KVQ_EINVAL;
   const int bits = ly->bits, Hkv = ly->H, hd = ly->hd;
   if (bits < 2 || bits > 4 || !kvq_gqa_supported(Hq, Hkv, hd) || ly->thr_k <= 0) return KVQ_EINVAL;
   // Dense-and-Sparse caches in the reference outlier format with the K mirror (the compact format is not taken)
@@ -351,9 +368,9 @@ int kvq_decode_step_gqa(const kvq_layer *ly, int Hq, int64_t col, const void *q,
   int rc = kvq_append_kv_fused(ly, col, k, v, acts_are_half, stream);
   if (rc) return rc;
   record(0, st);
-  rc = kvq_score_k_gqa(bits, q, acts_are_half, ly->kmat, scores, ly->klut_score ? ly->klut_score : ly->klut, Hq, Hkv, hd, L,
-                       ly->max_len, ly->rope_theta, ly->pos_offset, ly->koutliers_t, ly->kidx_t, n_out, inv, parts,
-                       p.n_parts, ws, p.score_ws, stream);
+  rc = kvq_score_k_gqa_rope(bits, q, acts_are_half, ly->kmat, scores, ly->klut_score ? ly->klut_score : ly->klut, Hq, Hkv,
+                            hd, L, ly->max_len, ly->rope_theta, ly->pos_offset, ly->koutliers_t, ly->kidx_t, n_out, inv,
+                            parts, p.n_parts, ws, p.score_ws, rope, stream);
   record(1, st);
   if (rc) return rc;
   rc = kvq_softmax_finish(scores, sink_scores, parts, p.n_parts, probs, sink_probs, Hq, L, n_sink, inv, v_sink, out, stream);

@@ -65,12 +65,14 @@ __device__ __forceinline__ float gqa_wave_sum(float v) {
 }
 
 // grid (token tiles of blockDim tokens, KV-head groups of hpw); dynamic LDS: hpw codebooks [128][2^BITS] f32
-template <int BITS, int GB>
-__global__ __launch_bounds__(256) void gqa_score_kernel(
+// RT (scaled RoPE, kvq.h: kvq_rope): frequencies from rt_freq [64] instead of powf(rope_theta, ..), and the attention
+// factor rt_af scales the lane's (cos, sin) once (and the sin / cos of each outlier entry); gqa_score_kernel_rt below
+template <int BITS, int GB, bool RT>
+__device__ __forceinline__ void gqa_score_body(
     const uint32_t *__restrict__ mat, const float *__restrict__ lut, const float *__restrict__ qp,
     const float *__restrict__ q32, const float *__restrict__ out_t, const int32_t *__restrict__ idx_t,
     float *__restrict__ mul, float *__restrict__ parts, int64_t L, int64_t max_len, int Hkv, int G, int hpw, int n_out,
-    int pos_offset, float rope_theta, float inv, int n_parts) {
+    int pos_offset, float rope_theta, float inv, int n_parts, const float *__restrict__ rt_freq, float rt_af) {
   constexpr int N = 1 << BITS;
   constexpr int WPH = kHeadDim / 32 * BITS;
   extern __shared__ float tab[];
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void gqa_score_kernel(
   __syncthreads();
   if (wt0 >= L) return;   // (no barrier below)
 
-  const float th_reg = rope_freq(rope_theta, lane);   // theta_j in lane j
+  const float th_reg = RT ? rt_freq[lane] : rope_freq(rope_theta, lane);   // theta_j in lane j
   const float posf = (float)((int)tc + pos_offset);
   // (every index into acc is a compile-time constant: static_for, so that the array lives in registers)
   float acc[kGqaMaxHpw * GB];
@@ -97,6 +99,10 @@ __global__ __launch_bounds__(256) void gqa_score_kernel(
     static_for<0, 32>([&](auto I) __attribute__((always_inline)) {
       constexpr int i = decltype(I)::value;
       sincos_rev(__shfl(th_reg, role * 32 + i) * posf, sv[i], cv[i]);
+      if constexpr (RT) {
+        sv[i] *= rt_af;
+        cv[i] *= rt_af;
+      }
     });
     static_for<0, kGqaMaxHpw>([&](auto HH) __attribute__((always_inline)) {
       constexpr int hh = decltype(HH)::value;
@@ -137,6 +143,10 @@ __global__ __launch_bounds__(256) void gqa_score_kernel(
       if (valid && val != 0.f && (unsigned)hk < (unsigned)nh) {
         float sn, c;
         sincos_rev(th * posf, sn, c);
+        if constexpr (RT) {
+          sn *= rt_af;
+          c *= rt_af;
+        }
         const float sg = ch < 64 ? sn : -sn;
         const float *qk = q32 + (int64_t)(h0 + hk) * G * kHeadDim;
         static_for<0, GB>([&](auto Gi) __attribute__((always_inline)) {
@@ -175,6 +185,26 @@ __global__ __launch_bounds__(256) void gqa_score_kernel(
       });
     }
   });
+}
+
+template <int BITS, int GB>
+__global__ __launch_bounds__(256) void gqa_score_kernel(
+    const uint32_t *__restrict__ mat, const float *__restrict__ lut, const float *__restrict__ qp,
+    const float *__restrict__ q32, const float *__restrict__ out_t, const int32_t *__restrict__ idx_t,
+    float *__restrict__ mul, float *__restrict__ parts, int64_t L, int64_t max_len, int Hkv, int G, int hpw, int n_out,
+    int pos_offset, float rope_theta, float inv, int n_parts) {
+  gqa_score_body<BITS, GB, false>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv, G, hpw, n_out, pos_offset,
+                                  rope_theta, inv, n_parts, nullptr, 1.f);
+}
+
+template <int BITS, int GB>
+__global__ __launch_bounds__(256) void gqa_score_kernel_rt(
+    const uint32_t *__restrict__ mat, const float *__restrict__ lut, const float *__restrict__ qp,
+    const float *__restrict__ q32, const float *__restrict__ out_t, const int32_t *__restrict__ idx_t,
+    float *__restrict__ mul, float *__restrict__ parts, int64_t L, int64_t max_len, int Hkv, int G, int hpw, int n_out,
+    int pos_offset, float inv, int n_parts, const float *__restrict__ rt_freq, float rt_af) {
+  gqa_score_body<BITS, GB, true>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv, G, hpw, n_out, pos_offset,
+                                 0.f, inv, n_parts, rt_freq, rt_af);
 }
 
 // grid (token chunks, Hkv), 256 lanes: wave w, lane l -> channel octet o = 4w + l/16 (channels 8o .. 8o+7), token quad
@@ -332,10 +362,15 @@ template <int BITS>
 static int launch_score(int GB, dim3 grid, dim3 block, size_t lds, hipStream_t st, const uint32_t *mat, const float *lut,
                         const float *qp, const float *q32, const float *out_t, const int32_t *idx_t, float *mul,
                         float *parts, int64_t L, int64_t max_len, int Hkv, int G, int hpw, int n_out, int pos_offset,
-                        float theta, float inv, int n_parts) {
-#define KVQ_GQA_SCORE(B)                                                                                            \
-  gqa_score_kernel<BITS, B><<<grid, block, lds, st>>>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv, G, \
-                                                      hpw, n_out, pos_offset, theta, inv, n_parts)
+                        float theta, float inv, int n_parts, const kvq_rope *rope) {
+#define KVQ_GQA_SCORE(B)                                                                                              \
+  if (rope)                                                                                                           \
+    gqa_score_kernel_rt<BITS, B><<<grid, block, lds, st>>>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv, \
+                                                           G, hpw, n_out, pos_offset, inv, n_parts, rope->inv_freq,      \
+                                                           rope->attention_factor);                                      \
+  else                                                                                                                \
+    gqa_score_kernel<BITS, B><<<grid, block, lds, st>>>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv,   \
+                                                        G, hpw, n_out, pos_offset, theta, inv, n_parts)
   switch (GB) {
     case 1: KVQ_GQA_SCORE(1); break;
     case 2: KVQ_GQA_SCORE(2); break;
@@ -382,7 +417,18 @@ int kvq_score_k_gqa(int bits, const void *q, int q_is_half, const int32_t *mat, 
                     int Hkv, int hd, int64_t L, int64_t max_len, float rope_theta, int pos_offset, const float *outliers_t,
                     const int32_t *outlier_idx_t, int n_out, float inv_sqrt_hd, float *softmax_parts, int n_parts,
                     void *workspace, size_t workspace_bytes, void *stream) {
-  if (bits < 2 || bits > 4 || !gqa_shape_ok(Hq, Hkv, hd) || !q || !mat || !mul || !lut) return KVQ_EINVAL;
+  return kvq_score_k_gqa_rope(bits, q, q_is_half, mat, mul, lut, Hq, Hkv, hd, L, max_len, rope_theta, pos_offset,
+                              outliers_t, outlier_idx_t, n_out, inv_sqrt_hd, softmax_parts, n_parts, workspace,
+                              workspace_bytes, nullptr, stream);
+}
+
+int kvq_score_k_gqa_rope(int bits, const void *q, int q_is_half, const int32_t *mat, float *mul, const float *lut, int Hq,
+                         int Hkv, int hd, int64_t L, int64_t max_len, float rope_theta, int pos_offset,
+                         const float *outliers_t, const int32_t *outlier_idx_t, int n_out, float inv_sqrt_hd,
+                         float *softmax_parts, int n_parts, void *workspace, size_t workspace_bytes, const kvq_rope *rope,
+                         void *stream) {
+  if (bits < 2 || bits > 4 || !gqa_shape_ok(Hq, Hkv, hd) || !q || !mat || !mul || !lut || !rope_ok(rope))
+    return KVQ_EINVAL;
   if (L <= 0 || L > max_len || max_len >= (1ll << 31) || pos_offset < 0) return KVQ_EINVAL;
   // token-contiguous mirror with values (the compact format is not taken), or no outliers at all
   if ((outliers_t == nullptr) != (outlier_idx_t == nullptr) || (outlier_idx_t && n_out <= 0) || n_out < 0) return KVQ_EINVAL;
@@ -411,12 +457,12 @@ int kvq_score_k_gqa(int bits, const void *q, int q_is_half, const int32_t *mat, 
   const int np = softmax_parts ? n_parts : 0;
   if (bits == 4)
     return launch_score<4>(GB, grid, block, lds, st, m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
-                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np);
+                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np, rope);
   if (bits == 3)
     return launch_score<3>(GB, grid, block, lds, st, m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
-                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np);
+                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np, rope);
   return launch_score<2>(GB, grid, block, lds, st, m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
-                         max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np);
+                         max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np, rope);
 }
 
 size_t kvq_mix_v_gqa_workspace_bytes(int bits, int Hq, int Hkv, int hd, int64_t L) {

@@ -8,6 +8,14 @@ namespace kvq {
 
 int &last_hip_error_ref();
 
+// a scaled-RoPE argument (kvq.h: kvq_rope) the kernels can take: NULL (the theta rule), or a 4-byte aligned table
+// pointer and a finite attention factor > 0 (the table's values live on the device and are the caller's to check)
+inline bool rope_ok(const kvq_rope *r) {
+  if (!r) return true;
+  const float af = r->attention_factor;
+  return r->inv_freq != nullptr && (reinterpret_cast<uintptr_t>(r->inv_freq) & 3) == 0 && __builtin_isfinite(af) && af > 0.f;
+}
+
 // Launch errors are sticky per thread until the next successful check.
 inline int check_launch() {
   hipError_t e = hipGetLastError();

@@ -47,14 +47,12 @@
 
 namespace kvq {
 
-template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED = false, bool COMPACT = false, int PAIR = 0>
-__global__ __launch_bounds__(NWAVES * 64, 4)
-void score_k_kernel(ScoreKArgs a) {
+// the kernel body; RT: scaled RoPE (frequency table + attention factor, score_k_tile_at), score_k_kernel_rt below
+template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED, bool COMPACT, int PAIR, bool RT>
+__device__ __forceinline__ void score_k_body(const ScoreKArgs &a, unsigned char *smem, const float *rt_freq, float rt_af) {
   using G = KGeom<BITS, SPARSE, NWAVES, TRANSPOSED, PAIR>;
   constexpr int T = G::T, NT = G::NT, SCS = G::SCS;
-  // static LDS: every table offset in the tile body is a compile-time constant that folds into ds immediates
-  __shared__ __attribute__((aligned(16))) unsigned char smem[G::SMEM_B];
-  const KTile kt = score_k_tile<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR>(a, smem);
+  const KTile kt = score_k_tile<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR, RT>(a, smem, rt_freq, rt_af);
   if constexpr (SPARSE) {
     float *sc = reinterpret_cast<float *>(smem + G::SC_OFF);
     const int tid = threadIdx.x;
@@ -126,6 +124,22 @@ void score_k_kernel(ScoreKArgs a) {
 #endif
 }
 
+template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED = false, bool COMPACT = false, int PAIR = 0>
+__global__ __launch_bounds__(NWAVES * 64, 4)
+void score_k_kernel(ScoreKArgs a) {
+  // static LDS: every table offset in the tile body is a compile-time constant that folds into ds immediates
+  __shared__ __attribute__((aligned(16))) unsigned char smem[KGeom<BITS, SPARSE, NWAVES, TRANSPOSED, PAIR>::SMEM_B];
+  score_k_body<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR, false>(a, smem, nullptr, 1.f);
+}
+
+// scaled RoPE: rt_freq = kvq_rope.inv_freq (device [64]), rt_af = kvq_rope.attention_factor
+template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED = false, bool COMPACT = false, int PAIR = 0>
+__global__ __launch_bounds__(NWAVES * 64, 4)
+void score_k_kernel_rt(ScoreKArgs a, const float *rt_freq, float rt_af) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[KGeom<BITS, SPARSE, NWAVES, TRANSPOSED, PAIR>::SMEM_B];
+  score_k_body<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR, true>(a, smem, rt_freq, rt_af);
+}
+
 static int cu_count() {
   static int cus = 0;
   if (cus == 0) {
@@ -175,7 +189,7 @@ static int pick_groups(int H, int64_t tiles, int q_len, int max_hpg, int slots) 
 }
 
 template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED = false, bool COMPACT = false, int PAIR = 0>
-static int launch_score(const ScoreKArgs &a0, int q_len, float rope_theta, hipStream_t st) {
+static int launch_score(const ScoreKArgs &a0, int q_len, float rope_theta, const kvq_rope *rope, hipStream_t st) {
   constexpr int T = NWAVES * 32;
   ScoreKArgs a = a0;
   const int64_t full_tiles = a.L / T;
@@ -202,7 +216,11 @@ static int launch_score(const ScoreKArgs &a0, int q_len, float rope_theta, hipSt
   a.trace = reinterpret_cast<unsigned long long *>(strtoull(getenv("KVQ_TRACE_PTR") ? getenv("KVQ_TRACE_PTR") : "0", nullptr, 0));
   if (!a.trace) return KVQ_EINVAL;
 #endif
-  score_k_kernel<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR><<<grid, block, 0, st>>>(a);
+  if (rope)
+    score_k_kernel_rt<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR><<<grid, block, 0, st>>>(a, rope->inv_freq,
+                                                                                              rope->attention_factor);
+  else
+    score_k_kernel<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR><<<grid, block, 0, st>>>(a);
   return check_launch();
 }
 
@@ -218,7 +236,7 @@ static int64_t big_tiles_from() {
 
 template <int BITS>
 static int dispatch_score(ScoreKArgs a, const float *lut, const void *q_in, int q_is_half, int tables_ready,
-                          void *ws, int q_len, float theta, bool sparse, hipStream_t st) {
+                          void *ws, int q_len, float theta, bool sparse, const kvq_rope *rope, hipStream_t st) {
   unsigned char *tab = reinterpret_cast<unsigned char *>(ws);
   float *q32 = reinterpret_cast<float *>(tab + (size_t)q_len * a.H * KTab<BITS>::BUF_B);
   if (!tables_ready) {
@@ -235,34 +253,34 @@ static int dispatch_score(ScoreKArgs a, const float *lut, const void *q_in, int 
     // fp32 pair-sum tables (round 6; decode, q_len = 1, mirror formats, >= 16K tokens): exact, half the look-ups, one
     // 1024-lane workgroup per CU (kvq_ktab.h: KTabPair32); shorter caches take the per-channel tables, which are always built
     if (a.pair == 2 && q_len == 1 && a.idx_t != nullptr && a.L >= 16384) {
-      return a.out_t == nullptr ? launch_score<3, true, 16, true, true, 2>(a, q_len, theta, st)
-                                : launch_score<3, true, 16, true, false, 2>(a, q_len, theta, st);
+      return a.out_t == nullptr ? launch_score<3, true, 16, true, true, 2>(a, q_len, theta, rope, st)
+                                : launch_score<3, true, 16, true, false, 2>(a, q_len, theta, rope, st);
     }
     // fp16 pair-sum tables (decode, q_len = 1, mirror formats): half the look-ups (kvq_ktab.h: KTabPair3)
     if (a.pair == 1 && q_len == 1 && a.idx_t != nullptr) {
       if (a.out_t == nullptr)
-        return a.L >= 16384 ? launch_score<3, true, 8, true, true, 1>(a, q_len, theta, st)
-                            : launch_score<3, true, 4, true, true, 1>(a, q_len, theta, st);
-      return a.L >= 16384 ? launch_score<3, true, 8, true, false, 1>(a, q_len, theta, st)
-                          : launch_score<3, true, 4, true, false, 1>(a, q_len, theta, st);
+        return a.L >= 16384 ? launch_score<3, true, 8, true, true, 1>(a, q_len, theta, rope, st)
+                            : launch_score<3, true, 4, true, true, 1>(a, q_len, theta, rope, st);
+      return a.L >= 16384 ? launch_score<3, true, 8, true, false, 1>(a, q_len, theta, rope, st)
+                          : launch_score<3, true, 4, true, false, 1>(a, q_len, theta, rope, st);
     }
   }
   // big tiles (8 waves) once there are enough of them, small tiles for short caches
   if (a.idx_t != nullptr && a.out_t == nullptr) {     // compact mirror
-    return a.L >= big_tiles_from() ? launch_score<BITS, true, 8, true, true>(a, q_len, theta, st)
-                        : launch_score<BITS, true, 4, true, true>(a, q_len, theta, st);
+    return a.L >= big_tiles_from() ? launch_score<BITS, true, 8, true, true>(a, q_len, theta, rope, st)
+                        : launch_score<BITS, true, 4, true, true>(a, q_len, theta, rope, st);
   }
   if (a.out_t != nullptr) {
-    return a.L >= big_tiles_from() ? launch_score<BITS, true, 8, true>(a, q_len, theta, st)
-                        : launch_score<BITS, true, 4, true>(a, q_len, theta, st);
+    return a.L >= big_tiles_from() ? launch_score<BITS, true, 8, true>(a, q_len, theta, rope, st)
+                        : launch_score<BITS, true, 4, true>(a, q_len, theta, rope, st);
   }
   // (row-layout outliers -- the legacy entry points: 4-wave tiles measured 53.0 -> 46.4 us at 32K and 105 -> 123 at 128K,
   //  profiles/r06_t_rows_ab.txt; not adopted: the fused-softmax form of the same call counts 256-token tiles from 16K on, and the
   //  two forms are held bit-identical -- tests/test_fused_gpu.py)
   if (a.L >= (sparse ? big_tiles_from() : (int64_t)16384)) {
-    return sparse ? launch_score<BITS, true, 8>(a, q_len, theta, st) : launch_score<BITS, false, 8>(a, q_len, theta, st);
+    return sparse ? launch_score<BITS, true, 8>(a, q_len, theta, rope, st) : launch_score<BITS, false, 8>(a, q_len, theta, rope, st);
   }
-  return sparse ? launch_score<BITS, true, 4>(a, q_len, theta, st) : launch_score<BITS, false, 4>(a, q_len, theta, st);
+  return sparse ? launch_score<BITS, true, 4>(a, q_len, theta, rope, st) : launch_score<BITS, false, 4>(a, q_len, theta, rope, st);
 }
 
 static size_t ws_bytes(int bits, int q_len, int H) {
@@ -321,9 +339,9 @@ static int score_entry(int bits, const void *q, int q_is_half, int tables_ready,
                        int pos_offset, const float *outliers, const int32_t *outlier_idx, int n_out, int accumulate,
                        void *workspace, size_t workspace_bytes, void *stream, float *sm_parts = nullptr,
                        float sm_inv = 0.f, int sm_nparts = 0, const float *outliers_t = nullptr,
-                       const int32_t *idx_t = nullptr, int pair = 0) {
+                       const int32_t *idx_t = nullptr, int pair = 0, const kvq_rope *rope = nullptr) {
   if ((!q && !tables_ready) || !mat || !mul || !lut || q_len <= 0 || H <= 0 || hd != kHeadDim || L < 0 ||
-      L > max_len || bits < 2 || bits > 4)
+      L > max_len || bits < 2 || bits > 4 || !rope_ok(rope))
     return KVQ_EINVAL;
   const bool sparse = outliers != nullptr || idx_t != nullptr;     // (idx_t alone: the compact mirror)
   if (sparse && ((outliers && !outlier_idx) || (outliers_t && !idx_t) || n_out <= 0 || n_out > 4096)) return KVQ_EINVAL;
@@ -358,9 +376,9 @@ static int score_entry(int bits, const void *q, int q_is_half, int tables_ready,
   if (sm_parts && (q_len != 1 || accumulate || !sparse)) return KVQ_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   switch (bits) {
-    case 4: return dispatch_score<4>(a, lut, q, q_is_half, tables_ready, workspace, q_len, rope_theta, sparse, st);
-    case 3: return dispatch_score<3>(a, lut, q, q_is_half, tables_ready, workspace, q_len, rope_theta, sparse, st);
-    default: return dispatch_score<2>(a, lut, q, q_is_half, tables_ready, workspace, q_len, rope_theta, sparse, st);
+    case 4: return dispatch_score<4>(a, lut, q, q_is_half, tables_ready, workspace, q_len, rope_theta, sparse, rope, st);
+    case 3: return dispatch_score<3>(a, lut, q, q_is_half, tables_ready, workspace, q_len, rope_theta, sparse, rope, st);
+    default: return dispatch_score<2>(a, lut, q, q_is_half, tables_ready, workspace, q_len, rope_theta, sparse, rope, st);
   }
 }
 
@@ -370,6 +388,15 @@ int kvq_score_k(int bits, const float *q, const int32_t *mat, float *mul, const 
                 void *stream) {
   return score_entry(bits, q, 0, 0, mat, mul, lut, q_len, H, hd, L, max_len, rope_theta, pos_offset, outliers,
                      outlier_idx, n_out, accumulate, workspace, workspace_bytes, stream);
+}
+
+int kvq_score_k_rope(int bits, const float *q, const int32_t *mat, float *mul, const float *lut, int q_len, int H,
+                     int hd, int64_t L, int64_t max_len, float rope_theta, int pos_offset, const float *outliers,
+                     const int32_t *outlier_idx, int n_out, int accumulate, void *workspace, size_t workspace_bytes,
+                     const kvq_rope *rope, void *stream) {
+  return score_entry(bits, q, 0, 0, mat, mul, lut, q_len, H, hd, L, max_len, rope_theta, pos_offset, outliers,
+                     outlier_idx, n_out, accumulate, workspace, workspace_bytes, stream, nullptr, 0.f, 0, nullptr, nullptr,
+                     0, rope);
 }
 
 
@@ -406,6 +433,15 @@ int kvq_score_k_prepared(int bits, const int32_t *mat, float *mul, const float *
                      outlier_idx, n_out, accumulate, workspace, workspace_bytes, stream);
 }
 
+int kvq_score_k_prepared_rope(int bits, const int32_t *mat, float *mul, const float *lut, int H, int hd, int64_t L,
+                              int64_t max_len, float rope_theta, int pos_offset, const float *outliers,
+                              const int32_t *outlier_idx, int n_out, int accumulate, void *workspace,
+                              size_t workspace_bytes, const kvq_rope *rope, void *stream) {
+  return score_entry(bits, nullptr, 0, 1, mat, mul, lut, 1, H, hd, L, max_len, rope_theta, pos_offset, outliers,
+                     outlier_idx, n_out, accumulate, workspace, workspace_bytes, stream, nullptr, 0.f, 0, nullptr, nullptr,
+                     0, rope);
+}
+
 /* tiles of the sparse score kernel = (max, sum) partials per head it can write; 0: no fusion for this shape */
 int kvq_score_k_softmax_parts(int bits, int64_t L, int sparse) {
   if (bits < 2 || bits > 4 || L <= 0 || !sparse) return 0;
@@ -430,12 +466,23 @@ int kvq_score_k_prepared_softmax_ex(int bits, const int32_t *mat, float *mul, co
                                     const float *outliers_t, const int32_t *outlier_idx_t, void *workspace,
                                     size_t workspace_bytes, float inv_sqrt_hd, float *softmax_parts, int n_parts,
                                     int flags, void *stream) {
+  return kvq_score_k_prepared_softmax_rope(bits, mat, mul, lut, H, hd, L, max_len, rope_theta, pos_offset, outliers,
+                                           outlier_idx, n_out, outliers_t, outlier_idx_t, workspace, workspace_bytes,
+                                           inv_sqrt_hd, softmax_parts, n_parts, flags, nullptr, stream);
+}
+
+int kvq_score_k_prepared_softmax_rope(int bits, const int32_t *mat, float *mul, const float *lut, int H, int hd,
+                                      int64_t L, int64_t max_len, float rope_theta, int pos_offset,
+                                      const float *outliers, const int32_t *outlier_idx, int n_out,
+                                      const float *outliers_t, const int32_t *outlier_idx_t, void *workspace,
+                                      size_t workspace_bytes, float inv_sqrt_hd, float *softmax_parts, int n_parts,
+                                      int flags, const kvq_rope *rope, void *stream) {
   if (!softmax_parts || (!outliers && !outlier_idx_t) || n_parts != kvq_score_k_softmax_parts(bits, L, 1))
     return KVQ_EINVAL;
   return score_entry(bits, nullptr, 0, 1, mat, mul, lut, 1, H, hd, L, max_len, rope_theta, pos_offset,
                      outlier_idx_t ? nullptr : outliers, outlier_idx_t ? nullptr : outlier_idx, n_out, 0, workspace,
                      workspace_bytes, stream, softmax_parts, inv_sqrt_hd, n_parts, outliers_t, outlier_idx_t,
-                     (flags & KVQ_SCORE_F32_PAIR_TABLES) ? 2 : ((flags & KVQ_SCORE_F16_PAIR_TABLES) ? 1 : 0));
+                     (flags & KVQ_SCORE_F32_PAIR_TABLES) ? 2 : ((flags & KVQ_SCORE_F16_PAIR_TABLES) ? 1 : 0), rope);
 }
 
 }  // extern "C"

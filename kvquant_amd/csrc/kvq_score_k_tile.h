@@ -143,8 +143,12 @@ struct KTile {
 // (tile_i, h0_i, nh_i): the tile and the head group; score_k_tile below derives them from the block index
 // PAIR (3 bit, implies TRANSPOSED): fp16 pair-sum tables (KTabPair3) -- one ds_read_b32 + one v_dot2_f32_f16 per TWO codes,
 // half2 (cos, sin) per rotation pair (32 instead of 64 trig registers).
-template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED, bool COMPACT, int PAIR = 0>
-__device__ __forceinline__ KTile score_k_tile_at(const ScoreKArgs &a, unsigned char *smem, int tile_i, int h0_i, int nh_i) {
+// RT (scaled RoPE, kvq.h: kvq_rope): the frequencies come from the table rt_freq [64] instead of the device powf of
+// rope_theta, and the attention factor rt_af scales the lane's (cos, sin) pairs and the sparse phase's query copy once per
+// tile -- no per-token or per-head work.  RT = false is the theta kernel, unchanged.
+template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED, bool COMPACT, int PAIR = 0, bool RT = false>
+__device__ __forceinline__ KTile score_k_tile_at(const ScoreKArgs &a, unsigned char *smem, int tile_i, int h0_i, int nh_i,
+                                                 const float *rt_freq = nullptr, float rt_af = 1.f) {
   static_assert(!TRANSPOSED || SPARSE, "the transposed mirror is a sparse variant");
   static_assert(!COMPACT || TRANSPOSED, "packed entries live in the mirror");
   static_assert(PAIR == 0 || (BITS == 3 && TRANSPOSED), "pair-sum tables: 3 bit, decode (mirror) variants");
@@ -287,7 +291,15 @@ __device__ __forceinline__ KTile score_k_tile_at(const ScoreKArgs &a, unsigned c
   int spc_all[2] = {0, 0};
 
   // RoPE frequency j lives in lane j of one VGPR (64 lanes = 64 frequencies); theta_of(j) is a wave shuffle
-  const float th_reg = rope_freq(a.rope_theta, lane);
+  float th_reg;
+  if constexpr (RT) {
+    // (an ordinary load, consumed by the empty asm right away: hipcc waits for it here, in front of every hand-issued
+    //  load of the tile, so that none of their counted waits below has to cover it)
+    th_reg = rt_freq[lane];
+    asm volatile("" : "+v"(th_reg)::"memory");
+  } else {
+    th_reg = rope_freq(a.rope_theta, lane);
+  }
   auto theta_of = [&](int j) { return __shfl(th_reg, j); };
   if constexpr (SPARSE) {
     for (int i = tid; i < T * SCS; i += NT) sc[i] = 0.f;
@@ -295,7 +307,8 @@ __device__ __forceinline__ KTile score_k_tile_at(const ScoreKArgs &a, unsigned c
     // reads both with ONE ds_read_b64 (the entries' channels are data: these reads are where the kernel's bank conflicts are)
     for (int i = tid; i < nh * kHeadDim; i += NT) {
       const int c = i & (kHeadDim - 1);
-      ql[KVQ_QL_PAIR ? (i - c) + ((c & 63) << 1) + (c >> 6) : i] = qb[h0 * kHeadDim + i];
+      if constexpr (RT) ql[KVQ_QL_PAIR ? (i - c) + ((c & 63) << 1) + (c >> 6) : i] = qb[h0 * kHeadDim + i] * rt_af;
+      else ql[KVQ_QL_PAIR ? (i - c) + ((c & 63) << 1) + (c >> 6) : i] = qb[h0 * kHeadDim + i];
     }
   }
 
@@ -432,6 +445,10 @@ __device__ __forceinline__ KTile score_k_tile_at(const ScoreKArgs &a, unsigned c
     const float ang = theta_of(role * 32 + i) * posf;
     float sn, c;
     sincos_rev(ang, sn, c);
+    if constexpr (RT) {
+      sn *= rt_af;
+      c *= rt_af;
+    }
     if constexpr (PAIR == 1) {
       csh[i] = h16x2{(_Float16)c, (_Float16)sn};
     } else {
@@ -893,11 +910,12 @@ __device__ __forceinline__ void score_k_block_map(const ScoreKArgs &a, int &tile
   }
 }
 
-template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED, bool COMPACT, int PAIR = 0>
-__device__ __forceinline__ KTile score_k_tile(const ScoreKArgs &a, unsigned char *smem) {
+template <int BITS, bool SPARSE, int NWAVES, bool TRANSPOSED, bool COMPACT, int PAIR = 0, bool RT = false>
+__device__ __forceinline__ KTile score_k_tile(const ScoreKArgs &a, unsigned char *smem, const float *rt_freq = nullptr,
+                                             float rt_af = 1.f) {
   int tile_i, h0_i, nh_i;
   score_k_block_map(a, tile_i, h0_i, nh_i);
-  return score_k_tile_at<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR>(a, smem, tile_i, h0_i, nh_i);
+  return score_k_tile_at<BITS, SPARSE, NWAVES, TRANSPOSED, COMPACT, PAIR, RT>(a, smem, tile_i, h0_i, nh_i, rt_freq, rt_af);
 }
 
 }  // namespace kvq

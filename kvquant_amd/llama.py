@@ -45,6 +45,7 @@ import torch.nn as nn
 
 from . import sharding
 from .attention import KVQuantAttention, gqa_groups
+from .rope import RopeSpec
 
 KNOBS = dict(dynamicrope=True, use_orig_sparse=False, first_few_fp16=0, maxseqlen=-1, abits=4, include_sparse=False)
 
@@ -81,6 +82,21 @@ def kv_heads_of(cfg):
     return int(n_kv)
 
 
+def rope_spec_of(model):
+    """the model's RoPE as a kvquant_amd.rope.RopeSpec: the config's rope_parameters (transformers >= 5) or rope_scaling
+    (4.x); for the fixed scaled types the frequencies and attention factor are the model's own rotary_emb's, so the
+    kernels rotate with exactly the table the model was run with.  ValueError for types the kernels do not take."""
+    spec = RopeSpec.from_config(model.config)
+    base = model.model if hasattr(model, "model") else model
+    emb = getattr(base, "rotary_emb", None)
+    inv = getattr(emb, "inv_freq", None)
+    if not spec.is_default and not spec.dynamic and torch.is_tensor(inv) and inv.numel() == 64:
+        # (the model's original_inv_freq: its dynamic update never touches the fixed types)
+        inv = getattr(emb, "original_inv_freq", inv)
+        spec.pin_table(inv, getattr(emb, "attention_scaling", 1.0))
+    return spec
+
+
 def patch_llama(model, sparsity_threshold=0.99, compact=False):
     """give every decoder layer's self_attn the compressed KV path.  `model`: LlamaForCausalLM / LlamaModel whose
     config carries the KVQuant fields (kvquant_config).  Caches are created on each layer's current device.
@@ -95,6 +111,7 @@ def patch_llama(model, sparsity_threshold=0.99, compact=False):
     if theta is None:      # transformers >= 5 keeps it in rope_parameters
         theta = (getattr(cfg, "rope_parameters", None) or {}).get("rope_theta", 10000.0)
     base = model.model if hasattr(model, "model") else model
+    rope = rope_spec_of(model)
     for layer in base.layers:
         attn = layer.self_attn
         dev = next(attn.parameters()).device
@@ -102,7 +119,8 @@ def patch_llama(model, sparsity_threshold=0.99, compact=False):
                                 include_sparse=cfg.include_sparse, first_few_fp16=cfg.first_few_fp16,
                                 maxseqlen=cfg.maxseqlen, rope_theta=float(theta), sparsity_threshold=sparsity_threshold,
                                 device=dev, dtype=next(attn.parameters()).dtype, make_proj=False, compact=compact,
-                                num_key_value_heads=None if n_kv == cfg.num_attention_heads else n_kv)
+                                num_key_value_heads=None if n_kv == cfg.num_attention_heads else n_kv,
+                                rope_scaling=rope)
         # plain attributes, like the reference's (ML:1440-1466): they do not follow module.to(); use set_devices
         object.__setattr__(attn, "kvq", core)
         object.__setattr__(attn, "kcache", core.kcache)

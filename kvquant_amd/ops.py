@@ -93,6 +93,22 @@ def _L():
     return _lib.lib()
 
 
+def _rope(rope, device):
+    """scaled RoPE argument of the _rope entry points: None (the theta rule) or (inv_freq f32 [64] on `device`,
+    attention factor) -> ctypes pointer to a struct kvq_rope, or None (include/kvq.h: kvq_rope)"""
+    if rope is None:
+        return None
+    inv, af = rope
+    if not (torch.is_tensor(inv) and tuple(inv.shape) == (64,)):
+        raise ValueError("rope: expected (inv_freq f32 [64], attention_factor)")
+    if inv.device != device:
+        raise ValueError("rope: the frequency table is on %s, the cache on %s" % (inv.device, device))
+    af = float(af)
+    if not (af > 0 and af < float("inf")):
+        raise ValueError("rope: attention factor %r must be finite and > 0" % af)
+    return ctypes.byref(_lib.Rope(_f(inv, "inv_freq"), af))
+
+
 def rope_freqs(theta, device=None):
     """theta_j = powf(theta, -2j/128), j < 64, as the score kernels evaluate them (on the device)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -163,8 +179,8 @@ def pack_v_sparse_parallel(bits, mat, lut_rows, x, lo, hi, col0=0):
 
 
 def score_k(bits, q, mat, mul, lut, L, theta, pos_offset, outliers=None, outlier_indices=None,
-            accumulate=True):
-    """q [q_len,H,128] f32, mul [q_len,H,L] f32 (in place)."""
+            accumulate=True, rope=None):
+    """q [q_len,H,128] f32, mul [q_len,H,L] f32 (in place).  rope: None (theta rule) or (inv_freq, attention factor)."""
     H, hd, max_len = _cache_dims(mat, bits)
     if q.dim() != 3 or mul.dim() != 3 or q.shape[0] != mul.shape[0]:
         raise ValueError("vec must be [q_len, H, head_dim] and mul [q_len, H, kcachelen]")
@@ -174,12 +190,15 @@ def score_k(bits, q, mat, mul, lut, L, theta, pos_offset, outliers=None, outlier
     with _Dev(q):
         nbytes = _L().kvq_score_k_workspace_bytes(bits, q.shape[0], H)
         ws = _workspace(q.device, nbytes, slot="score")
-        _lib.check(_L().kvq_score_k(
-            bits, _f(q, "vec"), _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), q.shape[0], H, hd,
-            int(L), max_len, float(theta), int(pos_offset),
-            None if outliers is None else _f(outliers, "outliers"),
-            None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out,
-            1 if accumulate else 0, ws.data_ptr(), ws.numel(), _stream()), "kvq_score_k")
+        args = (bits, _f(q, "vec"), _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), q.shape[0], H, hd,
+                int(L), max_len, float(theta), int(pos_offset),
+                None if outliers is None else _f(outliers, "outliers"),
+                None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out,
+                1 if accumulate else 0, ws.data_ptr(), ws.numel())
+        if rope is None:
+            _lib.check(_L().kvq_score_k(*args, _stream()), "kvq_score_k")
+        else:
+            _lib.check(_L().kvq_score_k_rope(*args, _rope(rope, mat.device), _stream()), "kvq_score_k_rope")
 
 
 def outlier_mirror_rows(outliers, outlier_indices, outliers_t, outlier_indices_t, t0, t1):
@@ -453,33 +472,40 @@ def decode_prologue(bits, kmat, klut, klut_off, k, lo, hi, koutl, kidx, kcol, vm
 
 
 def score_k_prepared(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers=None, outlier_indices=None,
-                     accumulate=False):
+                     accumulate=False, rope=None):
     """score kernel only (q_len = 1); tables + q were written to `ws` by decode_prologue."""
     H, hd, max_len = _cache_dims(mat, bits)
     n_out = 0 if outliers is None else outliers.shape[1]
     with _Dev(mat):
-        _lib.check(_L().kvq_score_k_prepared(
-            bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
-            int(pos_offset), None if outliers is None else _f(outliers, "outliers"),
-            None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out, 1 if accumulate else 0,
-            ws.data_ptr(), ws.numel(), _stream()), "kvq_score_k_prepared")
+        args = (bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
+                int(pos_offset), None if outliers is None else _f(outliers, "outliers"),
+                None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out, 1 if accumulate else 0,
+                ws.data_ptr(), ws.numel())
+        if rope is None:
+            _lib.check(_L().kvq_score_k_prepared(*args, _stream()), "kvq_score_k_prepared")
+        else:
+            _lib.check(_L().kvq_score_k_prepared_rope(*args, _rope(rope, mat.device), _stream()),
+                       "kvq_score_k_prepared_rope")
 
 
 def score_k_prepared_softmax(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, outlier_indices, inv_sqrt_hd,
-                             n_parts, outliers_t=None, outlier_indices_t=None, f16_pair=False):
+                             n_parts, outliers_t=None, outlier_indices_t=None, f16_pair=False, rope=None):
     """sparse score kernel (tables already in `ws`, accumulate = 0) that also writes the per-(head, tile)
     softmax partials; returns the partials buffer (a workspace: consume it before the next call).
     f16_pair (3 bit, with the mirror): read the fp16 pair-sum tables (include/kvq.h: KVQ_SCORE_F16_PAIR_TABLES)."""
     H, hd, max_len = _cache_dims(mat, bits)
     with _Dev(mat):
         parts = _workspace(mat.device, H * n_parts * 8, slot="softmax")
-        _lib.check(_L().kvq_score_k_prepared_softmax_ex(
-            bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
-            int(pos_offset), _f(outliers, "outliers"), _i(outlier_indices, "outlier_indices"), outliers.shape[1],
-            *_mirror(outliers_t, outlier_indices_t, outliers.shape[1] // 2, max_len),
-            ws.data_ptr(), ws.numel(), float(inv_sqrt_hd), parts.data_ptr(), n_parts,
-            _lib.SCORE_F16_PAIR_TABLES if f16_pair else 0, _stream()),
-            "kvq_score_k_prepared_softmax_ex")
+        args = (bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
+                int(pos_offset), _f(outliers, "outliers"), _i(outlier_indices, "outlier_indices"), outliers.shape[1],
+                *_mirror(outliers_t, outlier_indices_t, outliers.shape[1] // 2, max_len),
+                ws.data_ptr(), ws.numel(), float(inv_sqrt_hd), parts.data_ptr(), n_parts,
+                _lib.SCORE_F16_PAIR_TABLES if f16_pair else 0)
+        if rope is None:
+            _lib.check(_L().kvq_score_k_prepared_softmax_ex(*args, _stream()), "kvq_score_k_prepared_softmax_ex")
+        else:
+            _lib.check(_L().kvq_score_k_prepared_softmax_rope(*args, _rope(rope, mat.device), _stream()),
+                       "kvq_score_k_prepared_softmax_rope")
     return parts
 
 
@@ -503,7 +529,7 @@ def softmax_finish(scores, parts, n_parts, inv_sqrt_hd, sink_scores=None, v_sink
 
 
 def score_k_softmax(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, outlier_indices, inv_sqrt_hd,
-                    sink_scores=None, outliers_t=None, outlier_indices_t=None, v_sink=None, sink_out=None):
+                    sink_scores=None, outliers_t=None, outlier_indices_t=None, v_sink=None, sink_out=None, rope=None):
     """q.K^T (tables already in `ws`) + softmax: `mul` [1, H, L] receives the raw scores; returns
     (probs f32 [H, L] holding fp16 values, sink_probs f16 [H, n_sink] or None).  Sparse caches take the
     score kernel with the first softmax pass fused in (2 launches), others score_k_prepared +
@@ -512,16 +538,16 @@ def score_k_softmax(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, out
     if n_parts == 0:
         if v_sink is not None:
             raise ValueError("v_sink needs the fused softmax partials (sparse cache)")
-        score_k_prepared(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, outlier_indices)
+        score_k_prepared(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, outlier_indices, rope=rope)
         return softmax_scale(mul[0], inv_sqrt_hd, sink_scores)
     parts = score_k_prepared_softmax(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, outlier_indices,
-                                     inv_sqrt_hd, n_parts, outliers_t, outlier_indices_t)
+                                     inv_sqrt_hd, n_parts, outliers_t, outlier_indices_t, rope=rope)
     return softmax_finish(mul[0], parts, n_parts, inv_sqrt_hd, sink_scores, v_sink, sink_out)
 
 
 def score_k_mix_v(bits, kmat, scores, klut, L, theta, pos_offset, ws, koutliers, koutlier_indices, inv_sqrt_hd,
                   vmat, out, vlut_rows, voutliers, voutlier_indices, sink_scores=None, koutliers_t=None,
-                  koutlier_indices_t=None, v_sink=None, f16_pair=False):
+                  koutlier_indices_t=None, v_sink=None, f16_pair=False, rope=None):
     """q.K^T (tables already in `ws`) -> softmax -> p.V of one decode token in two streaming launches + the slab
     reduce: the score kernel writes raw scores and per-tile softmax partials, the p.V kernel normalises on the way
     (kvq_mix_v_softmax).  scores [1, H, L] scratch, out f32 [1, H, hd].  Returns sink_probs (f16 [H, n_sink]) or None."""
@@ -529,12 +555,13 @@ def score_k_mix_v(bits, kmat, scores, klut, L, theta, pos_offset, ws, koutliers,
     if n_parts == 0 or voutliers is None:
         probs, sink_probs = score_k_softmax(bits, kmat, scores, klut, L, theta, pos_offset, ws, koutliers,
                                             koutlier_indices, inv_sqrt_hd, sink_scores, koutliers_t,
-                                            koutlier_indices_t, v_sink, out)
+                                            koutlier_indices_t, v_sink, out, rope=rope)
         mix_v(bits, probs.unsqueeze(0), vmat, out, vlut_rows, L, voutliers, voutlier_indices,
               accumulate=v_sink is not None)
         return sink_probs
     parts = score_k_prepared_softmax(bits, kmat, scores, klut, L, theta, pos_offset, ws, koutliers, koutlier_indices,
-                                     inv_sqrt_hd, n_parts, koutliers_t, koutlier_indices_t, f16_pair=f16_pair)
+                                     inv_sqrt_hd, n_parts, koutliers_t, koutlier_indices_t, f16_pair=f16_pair,
+                                     rope=rope)
     return mix_v_softmax(bits, scores, parts, n_parts, inv_sqrt_hd, vmat, out, vlut_rows, L, voutliers,
                          voutlier_indices, sink_scores, v_sink)
 
@@ -674,7 +701,7 @@ def make_layer(kc, vc, table, lut_off):
     return ly, (vstruct, table, lut_off, mix)
 
 
-def decode_step(layer, col, q, k, v, out, fuse_softmax, sinks=None, v_sink=None, sink_probs=None):
+def decode_step(layer, col, q, k, v, out, fuse_softmax, sinks=None, v_sink=None, sink_probs=None, rope=None):
     """kvq_decode_step: prologue + q.K^T + softmax + p.V + reduce of one layer from ONE library call.  layer: struct
     from make_layer; col: append column (cached tokens before this one, sink tokens not counted); q [H, 128], k, v
     [C]: all fp16 or all fp32; out f32 [1, H, hd].  sinks = (k_sink, sink_scores (out), inv_sqrt_hd) with v_sink /
@@ -693,11 +720,14 @@ def decode_step(layer, col, q, k, v, out, fuse_softmax, sinks=None, v_sink=None,
         nbytes = _L().kvq_decode_step_workspace_bytes(layer.bits, layer.H, layer.hd, int(col) + 1)
         ws = _workspace(out.device, nbytes + 256, slot="step")
         base = (ws.data_ptr() + 255) & ~255
-        _lib.check(_L().kvq_decode_step(
-            ctypes.byref(layer), int(col), int(col), qp, kp, vp, kh, None if sk is None else ctypes.byref(sk),
-            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
-            None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax),
-            base, ws.numel() - (base - ws.data_ptr()), _stream()), "kvq_decode_step")
+        args = (ctypes.byref(layer), int(col), int(col), qp, kp, vp, kh, None if sk is None else ctypes.byref(sk),
+                None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
+                None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax),
+                base, ws.numel() - (base - ws.data_ptr()))
+        if rope is None:
+            _lib.check(_L().kvq_decode_step(*args, _stream()), "kvq_decode_step")
+        else:
+            _lib.check(_L().kvq_decode_step_rope(*args, _rope(rope, out.device), _stream()), "kvq_decode_step_rope")
 
 
 # ---- prefill attention on the matrix cores ----------------------------------------------------------------------
@@ -752,7 +782,7 @@ def gqa_supported(Hq, Hkv, hd=128):
 
 
 def score_k_gqa(bits, q, mat, mul, lut, L, theta, pos_offset, outliers_t=None, outlier_indices_t=None, inv_sqrt_hd=None,
-                parts=None):
+                parts=None, rope=None):
     """kvq_score_k_gqa: raw scores mul f32 [Hq, L] of q [Hq, 128] (fp32 or fp16) over a cache of Hkv heads; K outliers
     from the token-contiguous mirror [n_out, max_len] (or none).  parts (optional): f32 [Hq, n_parts, 2] that receives
     the first softmax pass (n_parts = score_k_gqa_parts(L))."""
@@ -765,12 +795,15 @@ def score_k_gqa(bits, q, mat, mul, lut, L, theta, pos_offset, outliers_t=None, o
         if nbytes == 0:
             raise ValueError("score_k_gqa: unsupported shape (Hq=%d, Hkv=%d, bits=%d)" % (Hq, Hkv, bits))
         ws = _workspace(mul.device, nbytes, slot="gqa_score")
-        _lib.check(_L().kvq_score_k_gqa(
-            bits, qp, qh, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lut"), Hq, Hkv, hd, int(L), max_len, float(theta),
-            int(pos_offset), _fo(outliers_t, "outliers_t"), _io(outlier_indices_t, "outlier_indices_t"), n_out,
-            float(inv_sqrt_hd if inv_sqrt_hd is not None else 1.0 / hd ** 0.5),
-            None if parts is None else _f(parts, "parts"), 0 if parts is None else parts.shape[1],
-            ws.data_ptr(), ws.numel(), _stream()), "kvq_score_k_gqa")
+        args = (bits, qp, qh, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lut"), Hq, Hkv, hd, int(L), max_len, float(theta),
+                int(pos_offset), _fo(outliers_t, "outliers_t"), _io(outlier_indices_t, "outlier_indices_t"), n_out,
+                float(inv_sqrt_hd if inv_sqrt_hd is not None else 1.0 / hd ** 0.5),
+                None if parts is None else _f(parts, "parts"), 0 if parts is None else parts.shape[1],
+                ws.data_ptr(), ws.numel())
+        if rope is None:
+            _lib.check(_L().kvq_score_k_gqa(*args, _stream()), "kvq_score_k_gqa")
+        else:
+            _lib.check(_L().kvq_score_k_gqa_rope(*args, _rope(rope, mul.device), _stream()), "kvq_score_k_gqa_rope")
     return mul
 
 
@@ -795,7 +828,7 @@ def mix_v_gqa(bits, p, mat, mul, lut_rows, L, outliers=None, outlier_indices=Non
     return mul
 
 
-def decode_step_gqa(layer, Hq, col, q, k, v, out, sink_scores=None, v_sink=None, sink_probs=None):
+def decode_step_gqa(layer, Hq, col, q, k, v, out, sink_scores=None, v_sink=None, sink_probs=None, rope=None):
     """kvq_decode_step_gqa: append + grouped q.K^T + softmax + grouped p.V of one layer from ONE library call.
     layer: struct from make_layer (layer.H = KV heads); q [Hq, 128], k, v [Hkv*128]: all fp16 or all fp32; out f32
     [1, Hq, hd].  sink_scores: fp16 [Hq, n_sink] already scaled (sink_probs receives their probabilities);
@@ -812,12 +845,16 @@ def decode_step_gqa(layer, Hq, col, q, k, v, out, sink_scores=None, v_sink=None,
             raise ValueError("decode_step_gqa: unsupported shape (Hq=%d, Hkv=%d)" % (Hq, layer.H))
         ws = _workspace(out.device, nbytes + 256, slot="step")
         base = (ws.data_ptr() + 255) & ~255
-        _lib.check(_L().kvq_decode_step_gqa(
-            ctypes.byref(layer), int(Hq), int(col), qp, kp, vp, kh,
-            None if sink_scores is None else _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
-            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
-            None if sink_probs is None else _chk(sink_probs, torch.float16, "sink_probs"), _f(out, "out"),
-            base, ws.numel() - (base - ws.data_ptr()), _stream()), "kvq_decode_step_gqa")
+        args = (ctypes.byref(layer), int(Hq), int(col), qp, kp, vp, kh,
+                None if sink_scores is None else _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
+                None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
+                None if sink_probs is None else _chk(sink_probs, torch.float16, "sink_probs"), _f(out, "out"),
+                base, ws.numel() - (base - ws.data_ptr()))
+        if rope is None:
+            _lib.check(_L().kvq_decode_step_gqa(*args, _stream()), "kvq_decode_step_gqa")
+        else:
+            _lib.check(_L().kvq_decode_step_gqa_rope(*args, _rope(rope, out.device), _stream()),
+                       "kvq_decode_step_gqa_rope")
 
 
 def prefill_attention_gqa(q, k, v, softmax_scale=None):
@@ -842,7 +879,7 @@ def prefill_attention_gqa(q, k, v, softmax_scale=None):
 
 
 # ---- a chunk of S new tokens over the compressed cache (MFMA flash kernel, kvq_chunk_attn.hip) ---------------------
-def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None):
+def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=None):
     """kvq_chunk_attention: query i of q (fp16 [Hq, S, 128] view, contiguous last dimension; RoPE'd at position
     pos_offset + c0 + i) over the fp16 sink tokens and the compressed columns [0, c0 + i] of the layer (struct from
     make_layer, layer.H = KV heads; the chunk must already be packed into columns c0 .. c0+S-1).  k_sink fp16
@@ -863,9 +900,13 @@ def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None):
             raise ValueError("chunk_attention: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
         ws = _workspace(out.device, nbytes + 256, slot="chunk")
         base = (ws.data_ptr() + 255) & ~255
-        _lib.check(_L().kvq_chunk_attention(
-            ctypes.byref(layer), int(Hq), int(S), int(c0), q.data_ptr(), q.stride(0), q.stride(1),
-            None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
-            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
-            base, ws.numel() - (base - ws.data_ptr()), _stream()), "kvq_chunk_attention")
+        args = (ctypes.byref(layer), int(Hq), int(S), int(c0), q.data_ptr(), q.stride(0), q.stride(1),
+                None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
+                None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
+                base, ws.numel() - (base - ws.data_ptr()))
+        if rope is None:
+            _lib.check(_L().kvq_chunk_attention(*args, _stream()), "kvq_chunk_attention")
+        else:
+            _lib.check(_L().kvq_chunk_attention_rope(*args, _rope(rope, out.device), _stream()),
+                       "kvq_chunk_attention_rope")
     return out

@@ -8,7 +8,10 @@ the decode route is timed for 64 steps and scaled to S (its step time grows by S
 L0 >= 32K and S <= 512; the rows say so with "decode_scaled_from").  The attention FLOP rate counts the two products
 of the causal chunk, 4 * S * (L0 + S / 2) * 128 * Hq, against the 2.5 PF of the fp16 matrix cores.
 
-usage: python tools/chunk_bench.py [--out FILE] [--reps N] [--quick]"""
+--rope llama3 (or yarn): every row also times kvq_chunk_attention with that scaled-RoPE table (tests/rope_check.py
+spec; LLaMA-3.1's parameters) -- attn_ms_rope and its ratio to the theta rule.
+
+usage: python tools/chunk_bench.py [--out FILE] [--reps N] [--quick] [--rope llama3]"""
 import argparse
 import json
 import os
@@ -47,7 +50,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="only L0 = 131072, S = 512, MHA (the acceptance row)")
+    ap.add_argument("--rope", default=None, help="also time the chunk attention with this scaled RoPE (llama3, yarn)")
     args = ap.parse_args()
+    rope_spec = None
+    if args.rope:
+        from tests import rope_check
+        rope_spec = rope_check.spec(args.rope)
     dev = "cuda:0"
     Hq = 32
     L0s = [131072] if args.quick else [4096, 32768, 131072]
@@ -72,6 +80,13 @@ def main():
                 def attn_only():
                     ops.chunk_attention(layer, Hq, L0, q)
                 t_attn = timed(attn_only, args.reps)
+                t_rope = None
+                if rope_spec is not None:
+                    tab = rope_spec.table(dev, L0 + S)
+
+                    def attn_rope():
+                        ops.chunk_attention(layer, Hq, L0, q, rope=tab)
+                    t_rope = timed(attn_rope, args.reps)
                 n = min(S, DECODE_MAX_STEPS)
                 qs = [q[:, i].contiguous() for i in range(n)]
                 ks = [k[:, :, i].reshape(-1).contiguous() for i in range(n)]
@@ -88,6 +103,8 @@ def main():
                          attn_pflops=flop / t_attn / 1e15, attn_share_of_2p5pf=flop / t_attn / PEAK,
                          decode_steps_ms=t_dec * 1e3, decode_scaled_from=n if n < S else None,
                          speedup_vs_decode=t_dec / t_chunk)
+                if t_rope is not None:
+                    r.update(rope=args.rope, attn_ms_rope=t_rope * 1e3, rope_over_theta=t_rope / t_attn)
                 rows.append(r)
                 print(json.dumps(r), flush=True)
         del kc, vc, kp, vp

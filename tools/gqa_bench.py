@@ -5,7 +5,10 @@ the grouped q.K^T and p.V launches (library events, as bench.py takes them), alg
 their fraction of 8 TB/s, and the same step for the MHA-expanded equivalent (decode_kv over 32-head caches of the same
 length: what a model with its KV heads repeated runs without GQA support).  Prints ONE JSON line.
 
-    python tools/gqa_bench.py [--ctx 4096,32768,131072] [--extra-bits 3,2] [--steps 8] [--warmup 3] [--layers 32]"""
+    python tools/gqa_bench.py [--ctx 4096,32768,131072] [--extra-bits 3,2] [--steps 8] [--warmup 3] [--layers 32]
+                              [--rope llama3]
+--rope llama3 (or yarn): the grouped step is timed once more with every layer's cache rotating with that scaled-RoPE
+table (tests/rope_check.py spec; LLaMA-3.1's parameters): rope_gqa_ms_per_step and its ratio to the theta rule."""
 import argparse
 import ctypes
 import json
@@ -142,6 +145,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--no-mha", action="store_true")
+    ap.add_argument("--rope", default=None, help="also time the grouped step with this scaled RoPE (llama3, yarn)")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -151,7 +155,7 @@ def main(argv=None):
     lines = []
     for bits, L in runs:
         # (a multiple of 256, as bench.py's: the MHA p.V kernel takes max_len % 4 == 0 only, other lengths run its slow fallback)
-        max_len = (L + a.warmup + a.steps + 8 + 255) // 256 * 256
+        max_len = (L + 2 * (a.warmup + a.steps) + 8 + 255) // 256 * 256
         rec = {"bits": bits, "ctx": L, "Hq": Hq, "Hkv": Hkv, "layers": a.layers}
         layers = [make_layer(bits, Hkv, L, max_len, 100 + i, dev) for i in range(a.layers)]
         n_out = layers[0][0].num_outliers
@@ -160,6 +164,14 @@ def main(argv=None):
         rec.update(gqa_ms_per_step=round(ms, 3), gqa_tokens_per_s=round(1000.0 / ms, 1), gqa_layer_us=round(lay, 2),
                    gqa_qk_us=round(qk, 2), gqa_pv_us=round(pv, 2), alg_bytes_qk=kb, alg_bytes_pv=vb,
                    frac_8tbs_qk=round(kb / (qk * 1e-6) / HBM, 3), frac_8tbs_pv=round(vb / (pv * 1e-6) / HBM, 3))
+        if a.rope:
+            from tests import rope_check
+            spec = rope_check.spec(a.rope)
+            for kc, _, _, _ in layers:
+                kc.rope = spec
+            ms_r, lay_r, qk_r, _ = run_step(layers, Hq, a.steps, a.warmup, dev, True)
+            rec.update(rope=a.rope, rope_gqa_ms_per_step=round(ms_r, 3), rope_gqa_qk_us=round(qk_r, 2),
+                       rope_over_theta=round(ms_r / ms, 4))
         del layers
         torch.cuda.empty_cache()
         if not a.no_mha:
