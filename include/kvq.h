@@ -79,6 +79,9 @@ extern "C" {
  *        kvq_score_k_prepared_softmax_rope, kvq_score_k_gqa_rope, kvq_decode_step_rope, kvq_decode_step_gqa_rope,
  *        kvq_chunk_attention_rope): the K rotation takes an explicit frequency table and attention factor.  Each existing
  *        entry is its _rope twin with rope = NULL; kvq_layer is unchanged.  Additive only, kvq_version() stays 403.
+ *        Later in 403: kvq_chunk_attention_grouped[_rope, _workspace_bytes]: the chunk attention for G >= 2 and S <= 32
+ *        (draft verification) with the K / V tile decoded once per KV head.  Additive only, kvq_version() stays 403;
+ *        kvq_chunk_attention[_rope] keeps its kernels and its results bit for bit.
  *        A binding checks `kvq_version() / 100 == KVQ_ABI_MAJOR`. */
 #define KVQ_ABI_MAJOR 4
 KVQ_API int kvq_version(void);
@@ -660,6 +663,25 @@ KVQ_API int kvq_chunk_attention_rope(const kvq_layer *layer, int Hq, int S, int6
                                      int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
                                      const uint16_t *v_sink, int n_sink, float *out, void *workspace,
                                      size_t workspace_bytes, const kvq_rope *rope, void *stream);
+
+/* ---- short chunks under grouped-query attention (draft verification) -------------------------------------------------
+ * kvq_chunk_attention[_rope] for G = Hq / layer->H >= 2 and 1 <= S <= 32: same arguments, same semantics, same partials
+ * and merge (deterministic), but a workgroup belongs to one KV head and one split of the column range -- wave w < G holds
+ * the S rows of query head hk * G + w -- so every 64-column K / V tile (codebook look-up, outlier residuals, RoPE, the
+ * fp16 sink tile) is decoded once for the G query heads of its group where kvq_chunk_attention decodes it per query head.
+ * Outputs equal kvq_chunk_attention's where the two plans split the columns alike, else agree to fp32 rounding.
+ * kvq_chunk_attention_grouped_workspace_bytes is 0 for shapes this variant does not take (G == 1, S > 32 and whatever
+ * kvq_chunk_attention_workspace_bytes refuses); the calls then return KVQ_EINVAL.  Validation as kvq_chunk_attention:
+ * KVQ_EINVAL / KVQ_EWORKSPACE before any launch.  rope = NULL: the theta rule. */
+KVQ_API size_t kvq_chunk_attention_grouped_workspace_bytes(int Hq, int Hkv, int S, int64_t c0);
+KVQ_API int kvq_chunk_attention_grouped(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q,
+                                        int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                        const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+KVQ_API int kvq_chunk_attention_grouped_rope(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q,
+                                             int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                             const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                             size_t workspace_bytes, const kvq_rope *rope, void *stream);
 
 /* ---- uncapped ("orig") Dense-and-Sparse variants, 4 bit only ------------------ */
 

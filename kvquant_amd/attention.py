@@ -184,6 +184,23 @@ class KVQuantAttention(nn.Module):
         self.kcache.reset()
         self.vcache.reset()
 
+    def rollback(self, n_tokens):
+        """Drop the newest n_tokens tokens from both caches (the rejected tail of a verified draft): QuantK.truncate /
+        QuantV.truncate.  Refused while the fp16 sink caches are still filling, and for tokens that live there."""
+        kc, vc = self.kcache, self.vcache
+        if kc.klen != vc.vlen:
+            raise ValueError("rollback: K and V caches are out of step (%d / %d tokens)" % (kc.klen, vc.vlen))
+        if kc.klen < self.first_few_fp16:
+            raise ValueError("rollback while the fp16 sink cache is still filling (len %d < %d)"
+                             % (kc.klen, self.first_few_fp16))
+        if getattr(kc, "use_orig_sparse", False):
+            raise NotImplementedError("rollback: the uncapped (orig) CSR state grows by concatenation")
+        if not 0 <= int(n_tokens) <= kc.klen - self.first_few_fp16:
+            raise ValueError("rollback(%d): %d compressed tokens behind the %d fp16 sink tokens"
+                             % (n_tokens, kc.klen - self.first_few_fp16, self.first_few_fp16))
+        kc.truncate(n_tokens)
+        vc.truncate(n_tokens)
+
     # ------------------------------------------------------------------ core (post-projection states)
     def attend(self, query_states, key_states, value_states):
         """query/key/value_states: [1, H, q_len, hd] (pre-RoPE), activation dtype.

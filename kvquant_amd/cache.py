@@ -45,6 +45,17 @@ def _pack_col0(length, sinks):
     return length - sinks
 
 
+def _truncate_columns(length, sinks, n_tokens):
+    """compressed columns [lo, hi) that truncate(n_tokens) drops from a cache of `length` tokens, `sinks` of them fp16
+    sink tokens that own no column"""
+    n = int(n_tokens)
+    hi = length - sinks
+    if n < 0 or n > max(hi, 0):
+        raise ValueError("truncate(%d): the cache holds %d compressed tokens behind its %d fp16 sink tokens"
+                         % (n, max(hi, 0), sinks))
+    return hi - n, hi
+
+
 def _default_device(device):
     if device is not None:
         return torch.device(device)
@@ -165,6 +176,24 @@ class QuantK(nn.Module):
                 if t is not None:
                     t.zero_()
             self._reset_csr(self.device)
+
+    def truncate(self, n_tokens):
+        """Drop the newest n_tokens compressed tokens (a rejected draft): klen moves back and every array in which a
+        column owns storage is zero again for the dropped columns, as reset() leaves it -- the cache is then bit for
+        bit the one that never saw them.  Cost proportional to n_tokens.  ValueError if it would cut into the fp16 sink
+        tokens (which count in klen) or below zero."""
+        if self.use_orig_sparse:
+            raise NotImplementedError("truncate: the uncapped (orig) CSR state grows by concatenation")
+        lo, hi = _truncate_columns(self.klen, self.first_few_fp16, n_tokens)
+        self.kcache[:, :, lo:hi] = 0
+        if self.include_sparse:
+            for t in (self.outliers, self.outlier_indices):
+                if t is not None:
+                    t[lo:hi] = 0
+            for t in (self.outliers_t, self.outlier_indices_t):
+                if t is not None:
+                    t[:, lo:hi] = 0
+        self.klen -= hi - lo
 
     def load_lookup_table(self, quantizer, include_sparse=True, sparsity_threshold=0.99, norm=False):
         """ML:437-501.  thresholds -> fp16; offset / range formed in fp16;
@@ -407,6 +436,20 @@ class QuantV(nn.Module):
             self.outlier_indices.zero_()
         if self.lookup_table2 is not None:
             self.lookup_table2.zero_()
+
+    def truncate(self, n_tokens):
+        """Drop the newest n_tokens compressed tokens (QuantK.truncate): vlen moves back; packed words, codebook rows
+        (both tables) and outlier rows of the dropped columns are zero again, as reset() leaves them."""
+        lo, hi = _truncate_columns(self.vlen, self.first_few_fp16, n_tokens)
+        self.vcache[:, :, lo:hi] = 0
+        self.lookup_table[lo:hi] = 0
+        if self.lookup_table2 is not None:
+            self.lookup_table2[lo:hi] = 0
+        if self.include_sparse:
+            if self.outliers is not None:
+                self.outliers[lo:hi] = 0
+            self.outlier_indices[lo:hi] = 0
+        self.vlen -= hi - lo
 
     def load_lookup_table(self, quantizer, include_sparse=True, sparsity_threshold=0.99, norm=False):
         """ML:1045-1066: only the sorted global centroids are kept; per-token

@@ -22,6 +22,11 @@
 // Parallelism: (query head x 256-row block) is 64 workgroups at Hq = 32, S = 512, so the column range is also split
 // across workgroups; each split writes (max, sum, unnormalised O) partials and chunk_attn_merge_kernel merges the splits
 // of a row in a fixed order (deterministic).  GQA: query head h reads KV head h / G (the tile is decoded per query head).
+//
+// Grouped variant (GR, kvq_chunk_attention_grouped: G >= 2, S <= 32 -- draft verification): a workgroup belongs to one KV
+// head and one split; wave w < G owns the S rows of query head hk * G + w (one 32-row MFMA block, rows >= S clamped
+// duplicates that are never written), waves >= G own no rows but decode with the others.  The tile is then decoded ONCE
+// for the G heads of the group instead of once per query head; partials and merge are unchanged.
 #include "kvq_common.h"
 #include "kvq_host.h"
 
@@ -85,7 +90,7 @@ __device__ __forceinline__ uint32_t pack_f16(float a, float b) {
   __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];        \
   __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow]; \
   __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
-template <int BITS, bool RT>
+template <int BITS, bool RT, bool GR = false>
 __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, float *theta, float *vrow, float *kst,
                                                 float *vst, unsigned char *k16, unsigned char *vt16, const float *rt_freq,
                                                 float rt_af) {
@@ -96,11 +101,20 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
   const int hi = lane >> 5, ql = lane & 31;
   const int split = (int)blockIdx.x % a.nsplit;
   const int rest = (int)blockIdx.x / a.nsplit;
-  const int h = rest % a.Hq;
-  const int qb = a.nqb - 1 - rest / a.Hq;              // late (long-row) query blocks first
-  const int hk = h / a.G;
+  int h, qb, hk;
+  if constexpr (GR) {                                  // rest = KV head; the wave's query head (waves >= G: rowless)
+    const int w = __builtin_amdgcn_readfirstlane(wave);
+    hk = rest;
+    h = hk * a.G + (w < a.G ? w : a.G - 1);
+    qb = 0;
+  } else {
+    h = rest % a.Hq;
+    qb = a.nqb - 1 - rest / a.Hq;                      // late (long-row) query blocks first
+    hk = h / a.G;
+  }
+  const bool has_rows = !GR || __builtin_amdgcn_readfirstlane(wave) < a.G;
   const int q0w = qb * kQW;
-  const int q0 = q0w + wave * kQB;
+  const int q0 = GR ? 0 : q0w + wave * kQB;
   const int qrow = q0 + ql;
   const int qrc = qrow < a.S ? qrow : a.S - 1;
   const int64_t ml = a.max_len;
@@ -132,7 +146,7 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
   // ---- S^T, mask, online softmax, O^T of one staged tile.  sink: key j of the tile is sink token j (no causal mask);
   // else key j is compressed column t0 + j, visible to row q iff t0 + j <= c0 + q (and < Lc)
   auto attend_tile = [&](bool sink, int64_t t0) __attribute__((always_inline)) {
-    const bool active = q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1);
+    const bool active = has_rows && q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1);
     if (!active) return;
     f32x16 sacc[2];
 #pragma unroll
@@ -315,7 +329,7 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
   }
 
   // ---- partials of this split: unnormalised O^T rows, (max in raw score units, sum)
-  if (qrow < a.S) {
+  if (has_rows && qrow < a.S) {
     const int64_t prow = ((int64_t)h * a.nsplit + split) * a.S + qrow;
     float *op = a.part_o + prow * kD;
 #pragma unroll
@@ -343,6 +357,18 @@ template <int BITS>
 __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel_rt(Args a, const float *rt_freq, float rt_af) {
   KVQ_CHUNK_LDS
   chunk_attn_body<BITS, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af);
+}
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_grouped_kernel(Args a) {
+  KVQ_CHUNK_LDS
+  chunk_attn_body<BITS, false, true>(a, klut, theta, vrow, kst, vst, k16, vt16, nullptr, 1.f);
+}
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_grouped_kernel_rt(Args a, const float *rt_freq, float rt_af) {
+  KVQ_CHUNK_LDS
+  chunk_attn_body<BITS, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af);
 }
 #undef KVQ_CHUNK_LDS
 
@@ -374,13 +400,15 @@ struct Plan {
 
 static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p) {
+// grouped: the plan of the grouped kernel (G >= 2, S <= 32): Hkv workgroup rows in place of Hq x nqb
+static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = false) {
   if (Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 8 || (int64_t)Hkv * kD > 8192 || S <= 0 || S > kMaxS || c0 < 0 ||
       c0 + S >= (int64_t(1) << 31))
     return false;
+  if (grouped && (Hq / Hkv < 2 || S > kQB)) return false;
   p.nqb = (S + kQW - 1) / kQW;
   const int64_t tiles = (c0 + S + kKV - 1) / kKV;
-  const int64_t base = (int64_t)Hq * p.nqb;
+  const int64_t base = grouped ? (int64_t)Hkv : (int64_t)Hq * p.nqb;
   int64_t ns = (kTargetWorkgroups + base - 1) / base;
   const int64_t cap = tiles / kMinTilesPerSplit > 1 ? tiles / kMinTilesPerSplit : 1;
   if (ns > cap) ns = cap;
@@ -400,29 +428,16 @@ static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p) {
 
 using namespace kvq;
 
-extern "C" {
-
-size_t kvq_chunk_attention_workspace_bytes(int Hq, int Hkv, int S, int64_t c0) {
-  chunk::Plan p;
-  if (!chunk::plan(Hq, Hkv, S, c0, p)) return 0;
-  return p.o_bytes + p.ml_bytes;
-}
-
-int kvq_chunk_attention(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
-                        int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
-                        void *workspace, size_t workspace_bytes, void *stream) {
-  return kvq_chunk_attention_rope(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
-                                  workspace_bytes, nullptr, stream);
-}
-
-int kvq_chunk_attention_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
-                             int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
-                             void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream) {
+// grouped: the grouped kernel (one workgroup per KV head and split), which plan() takes for G >= 2 and S <= 32 only
+static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                                  int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink,
+                                  float *out, void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream,
+                                  bool grouped) {
   if (!ly || !q || !out || !rope_ok(rope)) return KVQ_EINVAL;
   const int bits = ly->bits;
   if ((bits != 2 && bits != 3 && bits != 4) || ly->hd != chunk::kD || ly->thr_k <= 0) return KVQ_EINVAL;
   chunk::Plan p;
-  if (!chunk::plan(Hq, ly->H, S, c0, p)) return KVQ_EINVAL;
+  if (!chunk::plan(Hq, ly->H, S, c0, p, grouped)) return KVQ_EINVAL;
   if (ly->max_len <= 0 || ly->max_len >= (int64_t(1) << 31) || c0 + S > ly->max_len || ly->pos_offset < 0 ||
       c0 + S + ly->pos_offset >= (int64_t(1) << 31))
     return KVQ_EINVAL;
@@ -468,8 +483,18 @@ int kvq_chunk_attention_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, con
   a.rope_theta = ly->rope_theta;
   a.scale_log2e = (1.0f / sqrtf((float)chunk::kD)) * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)((int64_t)Hq * p.nqb * p.nsplit)), block(chunk::kThreads);
-  if (rope) {
+  const dim3 grid((unsigned)((int64_t)(grouped ? ly->H : Hq * p.nqb) * p.nsplit)), block(chunk::kThreads);
+  if (grouped && rope) {
+    const float *f = rope->inv_freq;
+    const float af = rope->attention_factor;
+    if (bits == 4) chunk::chunk_attn_grouped_kernel_rt<4><<<grid, block, 0, st>>>(a, f, af);
+    else if (bits == 3) chunk::chunk_attn_grouped_kernel_rt<3><<<grid, block, 0, st>>>(a, f, af);
+    else chunk::chunk_attn_grouped_kernel_rt<2><<<grid, block, 0, st>>>(a, f, af);
+  } else if (grouped) {
+    if (bits == 4) chunk::chunk_attn_grouped_kernel<4><<<grid, block, 0, st>>>(a);
+    else if (bits == 3) chunk::chunk_attn_grouped_kernel<3><<<grid, block, 0, st>>>(a);
+    else chunk::chunk_attn_grouped_kernel<2><<<grid, block, 0, st>>>(a);
+  } else if (rope) {
     const float *f = rope->inv_freq;
     const float af = rope->attention_factor;
     if (bits == 4) chunk::chunk_attn_kernel_rt<4><<<grid, block, 0, st>>>(a, f, af);
@@ -485,6 +510,49 @@ int kvq_chunk_attention_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, con
   chunk::chunk_attn_merge_kernel<<<(unsigned)((int64_t)S * Hq), chunk::kD, 0, st>>>(a.part_o, a.part_ml, out, Hq, S,
                                                                                      p.nsplit, a.scale_log2e);
   return check_launch();
+}
+
+extern "C" {
+
+size_t kvq_chunk_attention_workspace_bytes(int Hq, int Hkv, int S, int64_t c0) {
+  chunk::Plan p;
+  if (!chunk::plan(Hq, Hkv, S, c0, p)) return 0;
+  return p.o_bytes + p.ml_bytes;
+}
+
+int kvq_chunk_attention(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                        int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  return kvq_chunk_attention_rope(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                  workspace_bytes, nullptr, stream);
+}
+
+int kvq_chunk_attention_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                             int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                             void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream) {
+  return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, rope, stream, false);
+}
+
+size_t kvq_chunk_attention_grouped_workspace_bytes(int Hq, int Hkv, int S, int64_t c0) {
+  chunk::Plan p;
+  if (!chunk::plan(Hq, Hkv, S, c0, p, true)) return 0;
+  return p.o_bytes + p.ml_bytes;
+}
+
+int kvq_chunk_attention_grouped(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                                int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+  return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, nullptr, stream, true);
+}
+
+int kvq_chunk_attention_grouped_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                                     int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink,
+                                     float *out, void *workspace, size_t workspace_bytes, const kvq_rope *rope,
+                                     void *stream) {
+  return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, rope, stream, true);
 }
 
 }  // extern "C"

@@ -46,6 +46,7 @@ import torch.nn as nn
 from . import sharding
 from .attention import KVQuantAttention, gqa_groups
 from .rope import RopeSpec
+from .spec import MAX_DRAFT, accept_draft, ngram_draft
 
 KNOBS = dict(dynamicrope=True, use_orig_sparse=False, first_few_fp16=0, maxseqlen=-1, abits=4, include_sparse=False)
 
@@ -137,6 +138,21 @@ def reset_caches(model):
     base = model.model if hasattr(model, "model") else model
     for layer in base.layers:
         layer.self_attn.kvq.reset()
+
+
+def rollback(model, n_tokens):
+    """drop the newest n_tokens tokens from every layer's caches (KVQuantAttention.rollback): the rejected tail of a
+    verified draft.  The layers are checked first, so that a refusal leaves all of them as they were."""
+    base = model.model if hasattr(model, "model") else model
+    cores = [layer.self_attn.kvq for layer in base.layers]
+    for core in cores:
+        if getattr(core.kcache, "use_orig_sparse", False):
+            raise NotImplementedError("rollback: the uncapped (orig) CSR state grows by concatenation")
+        if core.kcache.klen != core.vcache.vlen or not 0 <= n_tokens <= core.kcache.klen - core.first_few_fp16:
+            raise ValueError("rollback(%d): a layer holds %d / %d tokens, %d of them fp16 sink tokens"
+                             % (n_tokens, core.kcache.klen, core.vcache.vlen, core.first_few_fp16))
+    for core in cores:
+        core.rollback(n_tokens)
 
 
 def load_quantizers(model, quantizers, include_sparse=True, sparsity_threshold=0.99, norm=False):
@@ -339,7 +355,8 @@ def _warp_logits(logits, temperature, top_k, top_p):
 
 @torch.no_grad()
 def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_id=None, pad_token_id=None,
-             do_sample=False, temperature=1.0, top_k=50, top_p=1.0, min_length=0, generator=None):
+             do_sample=False, temperature=1.0, top_k=50, top_p=1.0, min_length=0, generator=None, draft_len=0,
+             drafter=None, stats=None):
     """Decoding with the compressed cache: the reference's `model.generate(..., kvquant=True)`
     (generation/utils.py:2325-2416) -- the prompt goes through the model once (parallel pack of its K / V), then every
     step feeds ONLY the newest token (`input_ids = next_tokens[:, None]`, :2378-2380), the returned sequence is the
@@ -351,9 +368,21 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
     the conversation -- its positions follow the caches' length, and the whole follow-up prompt goes through the
     attention as one chunk over the compressed cache (KVQuantAttention.attend_multi -> cache.chunk_kv).  The returned
     sequence is `input_ids` with the new tokens appended (the earlier turns are in the caches, not in it).  Reset with
-    load_quantizers() or each layer's kvq.reset() to start a new conversation."""
+    load_quantizers() or each layer's kvq.reset() to start a new conversation.
+    draft_len = k (1 <= k <= 31; greedy only): speculative decoding.  Each round `drafter(seq, k)` (seq: the 1-D ids so
+    far; default ngram_draft, prompt lookup) proposes up to k tokens, `[last token] + draft` goes through the model as
+    ONE forward (one pass over the packed cache for all rows: cache.chunk_kv), the longest prefix of the draft that
+    equals the model's own arg-max is kept, the next token is the arg-max behind it, and the rejected tail leaves the
+    caches again (rollback).  The caches end as plain generate() leaves them; the tokens are the greedy ones up to
+    near-ties (a chunk's rows and a single token's take different split plans).  stats (a dict) receives `forwards`
+    (model calls, the prompt's included), `rounds` (those after the prompt), `drafted` and `accepted` (tokens)."""
     if input_ids.shape[0] != 1:
         raise ValueError("the compressed-cache path is batch 1 (ML:1408)")
+    if draft_len:
+        if do_sample:
+            raise ValueError("speculative decoding (draft_len > 0) is greedy: do_sample=True is not taken")
+        if not 1 <= int(draft_len) <= MAX_DRAFT:
+            raise ValueError("draft_len must be 0 (off) or 1 .. %d" % MAX_DRAFT)
     dev = model.gpus[0] if hasattr(model, "gpus") else next(model.parameters()).device
     input_ids = input_ids.to(dev)
     n_prompt = input_ids.shape[1]
@@ -363,6 +392,9 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
         eos_token_id = [eos_token_id]
     if eos_token_id is not None and pad_token_id is None:
         raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
+    if draft_len:
+        return _generate_speculative(model, input_ids, max_length, eos_token_id, min_length, int(draft_len),
+                                     drafter or ngram_draft, stats)
     seq = input_ids
     cur = input_ids
     unfinished = True
@@ -389,6 +421,48 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
     return seq
 
 
+def _generate_speculative(model, input_ids, max_length, eos_token_id, min_length, draft_len, drafter, stats):
+    """the draft_len > 0 loop of generate(): invariant at the top of a round -- the caches hold every token of `seq` but
+    the last, `feed` is that last token (first round: the prompt) followed by the draft"""
+    base = model.model if hasattr(model, "model") else model
+    core = base.layers[0].self_attn.kvq
+    seq, feed, draft = input_ids, input_ids, []
+    st = dict(rounds=0, drafted=0, accepted=0, forwards=0)
+    while True:
+        logits = model(feed, use_cache=False).logits[0, feed.shape[1] - 1 - len(draft):, :].float()
+        st["forwards"] += 1
+        st["rounds"] += seq is not input_ids
+        st["drafted"] += len(draft)
+        if eos_token_id is not None:
+            for i in range(min(logits.shape[0], min_length - seq.shape[1])):
+                logits[i, eos_token_id] = float("-inf")         # MinLengthLogitsProcessor at row i's length
+        n_acc, nxt = accept_draft(draft, logits.argmax(dim=-1).tolist())
+        new = draft[:n_acc] + [nxt]
+        st["accepted"] += n_acc
+        done = False
+        if eos_token_id is not None:
+            for i, t in enumerate(new):
+                if t in eos_token_id:                           # the first EOS ends it; nothing behind it is kept
+                    new, done = new[:i + 1], True
+                    break
+        back = len(draft) - (len(new) - 1)
+        if back:
+            rollback(model, back)
+        seq = torch.cat((seq, torch.tensor([new], dtype=seq.dtype, device=seq.device)), dim=-1)
+        if done or seq.shape[1] >= max_length:
+            break
+        # the next draft: never past max_length (the round adds len(draft) + 1 tokens at most) nor past the cache
+        klen, sinks = core.kcache.klen, core.first_few_fp16
+        k = min(draft_len, max_length - seq.shape[1] - 1, core.kcache.max_len - (klen - sinks) - 1)
+        draft = []
+        if k > 0 and klen >= sinks:
+            draft = [int(t) for t in drafter(seq[0], k)][:k]
+        feed = torch.tensor([new[-1:] + draft], dtype=seq.dtype, device=seq.device)
+    if stats is not None:
+        stats.update(st)
+    return seq
+
+
 def inference_main(argv=None):
     """lwm/llama_inference.py:39-138 (the same arguments): load a long-context Llama with the compressed cache sized by
     --maxseqlen, read the quantizer pickle, sample a continuation of --text and print it with the wall time.
@@ -410,6 +484,10 @@ def inference_main(argv=None):
     ap.add_argument("--norm", action="store_true", help="Whether to use q-norm.")
     ap.add_argument("--seed", type=int, default=None, help="(extra) seed of the sampler")
     ap.add_argument("--greedy", action="store_true", help="(extra) arg-max decoding instead of sampling")
+    ap.add_argument("--draft-len", type=int, default=0,
+                    help="(extra) speculative decoding: verify up to this many prompt-lookup draft tokens per forward "
+                         "(1 .. 31, with --greedy; 0: off)")
+    ap.add_argument("--ngram", type=int, default=3, help="(extra) longest n-gram the prompt-lookup drafter matches")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("kvquant_amd.llama needs a GPU (no CPU fallback)")
@@ -417,6 +495,8 @@ def inference_main(argv=None):
         raise SystemExit("--maxseqlen must be set: it sizes the preallocated compressed cache")
     if (args.text is None) == (args.token_ids is None):
         raise SystemExit("give the prompt as --text or as --token-ids")
+    if args.draft_len and (not args.greedy or args.abits == 16):
+        raise SystemExit("--draft-len needs --greedy and the compressed cache (--abits 2 / 3 / 4)")
     dev = torch.device("cuda:0")
     model = get_model(args.model, 2048, args.maxseqlen, args.abits if args.abits != 16 else 4, args.include_sparse,
                       args.first_few_fp16)
@@ -444,7 +524,8 @@ def inference_main(argv=None):
         t1 = time.time()
         with torch.no_grad():
             ids = generate(model, input_ids, max_length=args.max_length, min_length=args.min_length, eos_token_id=eos,
-                           pad_token_id=pad, do_sample=not args.greedy, generator=gen)
+                           pad_token_id=pad, do_sample=not args.greedy, generator=gen, draft_len=args.draft_len,
+                           drafter=lambda seq, k: ngram_draft(seq, k, max_ngram=args.ngram))
         torch.cuda.synchronize()
         t2 = time.time()
     else:

@@ -2,6 +2,7 @@
 raw device pointers + torch's current stream out.  Argument checks raise
 ValueError; a failing library call raises KvqError.  No CPU path."""
 import ctypes
+import os
 
 import torch
 
@@ -879,11 +880,27 @@ def prefill_attention_gqa(q, k, v, softmax_scale=None):
 
 
 # ---- a chunk of S new tokens over the compressed cache (MFMA flash kernel, kvq_chunk_attn.hip) ---------------------
+# Short chunks under grouped-query attention (G >= 2, S <= 32: draft verification) take the grouped kernel
+# (kvq_chunk_attention_grouped: a K / V tile is decoded once per KV head instead of once per query head).
+# KVQ_CHUNK_GROUPED=0 keeps the per-head kernel for every shape (A/B runs).
+CHUNK_GROUPED = os.environ.get("KVQ_CHUNK_GROUPED", "1") != "0"
+
+
+def chunk_attention_route(Hq, Hkv, S):
+    """which kernel chunk_attention runs for S query rows of Hq heads over Hkv KV heads: "grouped"
+    (kvq_chunk_attention_grouped) where the library takes the shape and CHUNK_GROUPED is on, else "heads"
+    (kvq_chunk_attention)"""
+    if CHUNK_GROUPED and _L().kvq_chunk_attention_grouped_workspace_bytes(int(Hq), int(Hkv), int(S), 0) > 0:
+        return "grouped"
+    return "heads"
+
+
 def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=None):
     """kvq_chunk_attention: query i of q (fp16 [Hq, S, 128] view, contiguous last dimension; RoPE'd at position
     pos_offset + c0 + i) over the fp16 sink tokens and the compressed columns [0, c0 + i] of the layer (struct from
     make_layer, layer.H = KV heads; the chunk must already be packed into columns c0 .. c0+S-1).  k_sink fp16
-    [Hkv, 128, n_sink] (post-RoPE) / v_sink fp16 [Hkv, n_sink, 128], or None.  Returns out f32 [S, Hq, 128]."""
+    [Hkv, 128, n_sink] (post-RoPE) / v_sink fp16 [Hkv, n_sink, 128], or None.  Returns out f32 [S, Hq, 128].
+    Shapes chunk_attention_route() sends to "grouped" run kvq_chunk_attention_grouped (same arguments and semantics)."""
     if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float16 and q.dim() == 3 and q.stride(2) == 1):
         raise ValueError("q: expected an fp16 GPU tensor [Hq, S, 128] with a contiguous last dimension")
     if q.shape[0] != Hq or q.shape[2] != 128:
@@ -895,7 +912,8 @@ def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=N
     if out is None:
         out = torch.empty((S, Hq, 128), dtype=torch.float32, device=q.device)
     with _Dev(out):
-        nbytes = _L().kvq_chunk_attention_workspace_bytes(int(Hq), layer.H, int(S), int(c0))
+        name = "kvq_chunk_attention_grouped" if chunk_attention_route(Hq, layer.H, S) == "grouped" else "kvq_chunk_attention"
+        nbytes = getattr(_L(), name + "_workspace_bytes")(int(Hq), layer.H, int(S), int(c0))
         if nbytes == 0:
             raise ValueError("chunk_attention: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
         ws = _workspace(out.device, nbytes + 256, slot="chunk")
@@ -905,8 +923,7 @@ def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=N
                 None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
                 base, ws.numel() - (base - ws.data_ptr()))
         if rope is None:
-            _lib.check(_L().kvq_chunk_attention(*args, _stream()), "kvq_chunk_attention")
+            _lib.check(getattr(_L(), name)(*args, _stream()), name)
         else:
-            _lib.check(_L().kvq_chunk_attention_rope(*args, _rope(rope, out.device), _stream()),
-                       "kvq_chunk_attention_rope")
+            _lib.check(getattr(_L(), name + "_rope")(*args, _rope(rope, out.device), _stream()), name + "_rope")
     return out
