@@ -202,39 +202,49 @@ class KVQuantAttention(nn.Module):
         vc.truncate(n_tokens)
 
     # ------------------------------------------------------------------ core (post-projection states)
+    def _sink_caches(self):
+        """(k_sink, v_sink) of decode_kv / chunk_kv: the fp16 sink caches, or (None, None) without sink tokens"""
+        if self.first_few_fp16 > 0:
+            return self.kcache_fp16[0], self.vcache_fp16[0]
+        return None, None
+
     def attend(self, query_states, key_states, value_states):
-        """query/key/value_states: [1, H, q_len, hd] (pre-RoPE), activation dtype.
-        Returns attn_output [1, q_len, hidden] (before o_proj).  Grouped-query attention: key / value_states carry
-        num_key_value_heads heads (attend_gqa)."""
-        if self.num_kv_groups > 1:
-            return self.attend_gqa(query_states, key_states, value_states)
+        """query_states: [1, H, q_len, hd], key / value_states: [1, num_key_value_heads, q_len, hd] (pre-RoPE),
+        activation dtype.  Returns attn_output [1, q_len, hidden] (before o_proj).  Grouped-query attention
+        (G = num_kv_groups > 1) runs the same three phases -- prefill, sink filling with the KV heads repeated per
+        group, one-call decode -- and refuses the configurations for which MHA falls back to the multi-launch tail."""
         bsz, H, q_len, hd = query_states.shape
         assert bsz == 1, "batch 1 only (ML:1801)"
         if q_len > 1 and self.kcache.klen > 0:
             return self.attend_multi(query_states, key_states, value_states)
+        G = self.num_kv_groups
         sinks = self.first_few_fp16
         key_states = key_states.half()
         value_states = value_states.half()
         start = self.kcache.klen
         cos, sin = self.rotary_emb(value_states, start, start + q_len)
         fused = self.kcache.include_sparse and self.vcache.include_sparse
-        if (q_len == 1 and fused and start >= sinks and query_states.dtype == torch.float16 and hd == 128
-                and (sinks == 0 or (self.fuse_sinks and self.kcache_fp16.dtype == torch.float16))):
-            # ---- decode over the compressed cache (ML:1948-2006), GPU-resident: the query's RoPE in one launch
-            # (kvq_rope_q_f16: torch's fp16 roundings), then one library call for the layer's KV path
-            q_rope = ops.rope_q_f16(query_states.reshape(H, hd), cos[0], sin[0])
-            if sinks > 0:
+        if G > 1 and not (fused and hd == 128):
+            raise ValueError("grouped-query attention needs include_sparse caches and head_dim 128")
+        if q_len == 1 and start >= sinks:
+            f16 = query_states.dtype == torch.float16 and (sinks == 0 or self.kcache_fp16.dtype == torch.float16)
+            if G > 1 and not f16:
+                raise ValueError("grouped-query attention decodes fp16 activations")
+            if f16 and fused and hd == 128 and (G > 1 or sinks == 0 or self.fuse_sinks):
+                # ---- decode over the compressed cache (ML:1948-2006), GPU-resident: the query's RoPE in one launch
+                # (kvq_rope_q_f16: torch's fp16 roundings), then one library call for the layer's KV path
+                # (kvq_decode_step; kvq_decode_step_gqa for G > 1)
+                q_rope = ops.rope_q_f16(query_states.reshape(H, hd), cos[0], sin[0])
+                k_sink, v_sink = self._sink_caches()
                 out, _ = decode_kv(self.kcache, self.vcache, q_rope, key_states.flatten(), value_states.flatten(),
-                                   k_sink=self.kcache_fp16[0], v_sink=self.vcache_fp16[0])
-            else:
-                out, _ = decode_kv(self.kcache, self.vcache, q_rope, key_states.flatten(), value_states.flatten())
-            return out.half().view(bsz, q_len, self.hidden_size)
+                                   k_sink=k_sink, v_sink=v_sink)
+                return out.half().view(bsz, q_len, self.hidden_size)
         query_rope = (query_states * cos) + (rotate_half(query_states) * sin)
 
         if q_len > 1 and self.kcache.klen == 0:
             # ---- prefill (ML:1861-1927) ------------------------------------------------------------
             key_rope = (key_states * cos) + (rotate_half(key_states) * sin)
-            # causal attention of the prompt on the matrix cores (kvq_prefill_attention, hand-written MFMA flash
+            # causal attention of the prompt on the matrix cores (kvq_prefill_attention[_gqa], hand-written MFMA flash
             # kernel; the reference calls flash-attn here, ML:1869-1873); output token-major, ready for o_proj
             attn_output = ops.prefill_attention(query_rope[0].half(), key_rope[0], value_states[0]) \
                 .view(bsz, q_len, self.hidden_size).to(query_states.dtype)
@@ -255,20 +265,22 @@ class KVQuantAttention(nn.Module):
         assert q_len == 1, "decode feeds one token at a time (generation/utils.py kvquant hooks)"
         inv = 1.0 / math.sqrt(hd)
         if self.kcache.klen < sinks:
-            # ---- still filling the fp16 sink caches (ML:1932-1946, 1981-1984) ------------------------
+            # ---- still filling the fp16 sink caches (ML:1932-1946, 1981-1984); G > 1: KV heads repeated per group
             key_rope = (key_states * cos) + (rotate_half(key_states) * sin)
             self.kcache_fp16[:, :, :, self.kcache.klen] = key_rope.transpose(2, 3).squeeze(-1)
             self.kcache.klen += 1
-            w = torch.matmul(query_rope, self.kcache_fp16[:, :, :, :self.kcache.klen]) / math.sqrt(hd)
+            ks = self.kcache_fp16[:, :, :, :self.kcache.klen]
+            w = torch.matmul(query_rope, ks if G == 1 else ks.repeat_interleave(G, dim=1)) / math.sqrt(hd)
             w = F.softmax(w, dim=-1, dtype=torch.float32).to(query_rope.dtype)
             self.vcache_fp16[:, :, self.vcache.vlen, :] = value_states.squeeze(2)
             self.vcache.vlen += 1
-            out = torch.matmul(w, self.vcache_fp16[:, :, :self.vcache.vlen, :])
+            vs = self.vcache_fp16[:, :, :self.vcache.vlen, :]
+            out = torch.matmul(w, vs if G == 1 else vs.repeat_interleave(G, dim=1))
             return out.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
 
-        # ---- decode over the compressed cache (ML:1948-2006), GPU-resident --------------------------
+        # ---- decode over the compressed cache (ML:1948-2006), GPU-resident, multi-launch (MHA only: for G > 1 the
+        # one-call decode above has returned or raised) ------------------------------------------------
         sink_scores = None
-        fused = self.kcache.include_sparse and self.vcache.include_sparse
         fuse_sinks = fused and sinks > 0 and self.fuse_sinks and self.kcache_fp16.dtype == torch.float16
         if sinks > 0 and not fuse_sinks:
             sink_scores = (torch.matmul(query_rope, self.kcache_fp16) / math.sqrt(hd))[0, :, 0, :].contiguous()
@@ -292,62 +304,6 @@ class KVQuantAttention(nn.Module):
         if sinks > 0:
             out = out + torch.matmul(sink_probs.view(1, H, 1, sinks), self.vcache_fp16)
         return out.transpose(1, 2).contiguous().reshape(bsz, q_len, self.hidden_size)
-
-    def attend_gqa(self, query_states, key_states, value_states):
-        """attend() for grouped-query attention: query_states [1, Hq, q_len, hd], key / value_states [1, Hkv, q_len, hd]
-        (pre-RoPE).  Prefill: kvq_prefill_attention_gqa + the packs of the Hkv heads; decode: kvq_rope_q_f16 over the Hq
-        heads + one kvq_decode_step_gqa; the sink-filling phase in torch with the KV heads repeated per group."""
-        bsz, H, q_len, hd = query_states.shape
-        assert bsz == 1, "batch 1 only (ML:1801)"
-        if q_len > 1 and self.kcache.klen > 0:
-            return self.attend_multi(query_states, key_states, value_states)
-        G = self.num_kv_groups
-        sinks = self.first_few_fp16
-        key_states = key_states.half()
-        value_states = value_states.half()
-        start = self.kcache.klen
-        cos, sin = self.rotary_emb(value_states, start, start + q_len)
-        if not (self.kcache.include_sparse and self.vcache.include_sparse and hd == 128):
-            raise ValueError("grouped-query attention needs include_sparse caches and head_dim 128")
-        if q_len == 1 and start >= sinks:
-            if query_states.dtype != torch.float16 or (sinks > 0 and self.kcache_fp16.dtype != torch.float16):
-                raise ValueError("grouped-query attention decodes fp16 activations")
-            q_rope = ops.rope_q_f16(query_states.reshape(H, hd), cos[0], sin[0])
-            if sinks > 0:
-                out, _ = decode_kv(self.kcache, self.vcache, q_rope, key_states.flatten(), value_states.flatten(),
-                                   k_sink=self.kcache_fp16[0], v_sink=self.vcache_fp16[0])
-            else:
-                out, _ = decode_kv(self.kcache, self.vcache, q_rope, key_states.flatten(), value_states.flatten())
-            return out.half().view(bsz, q_len, self.hidden_size)
-        query_rope = (query_states * cos) + (rotate_half(query_states) * sin)
-        key_rope = (key_states * cos) + (rotate_half(key_states) * sin)
-        if q_len > 1 and self.kcache.klen == 0:
-            attn_output = ops.prefill_attention_gqa(query_rope[0].half(), key_rope[0], value_states[0]) \
-                .view(bsz, q_len, self.hidden_size).to(query_states.dtype)
-            if sinks > 0:
-                n = min(sinks, q_len)
-                self.kcache_fp16[:, :, :, :n] = key_rope[:, :, :n, :].transpose(2, 3)
-                self.vcache_fp16[:, :, :n, :] = value_states[:, :, :n, :]
-                if q_len > sinks:
-                    self.kcache.parallel_pack(key_states[0, :, sinks:, :].transpose(1, 2))
-                    self.vcache.parallel_pack(value_states[0, :, sinks:, :].transpose(1, 2))
-                self.kcache.klen += n
-                self.vcache.vlen += n
-            else:
-                self.kcache.parallel_pack(key_states[0].transpose(1, 2))
-                self.vcache.parallel_pack(value_states[0].transpose(1, 2))
-            return attn_output
-        assert q_len == 1, "decode feeds one token at a time (generation/utils.py kvquant hooks)"
-        # ---- still filling the fp16 sink caches (ML:1932-1946, 1981-1984), KV heads repeated per group
-        self.kcache_fp16[:, :, :, self.kcache.klen] = key_rope.transpose(2, 3).squeeze(-1)
-        self.kcache.klen += 1
-        ks = self.kcache_fp16[:, :, :, :self.kcache.klen].repeat_interleave(G, dim=1)
-        w = torch.matmul(query_rope, ks) / math.sqrt(hd)
-        w = F.softmax(w, dim=-1, dtype=torch.float32).to(query_rope.dtype)
-        self.vcache_fp16[:, :, self.vcache.vlen, :] = value_states.squeeze(2)
-        self.vcache.vlen += 1
-        out = torch.matmul(w, self.vcache_fp16[:, :, :self.vcache.vlen, :].repeat_interleave(G, dim=1))
-        return out.transpose(1, 2).reshape(bsz, q_len, self.hidden_size)
 
     # ------------------------------------------------------------------ q_len > 1 on a warm cache
     def chunk_fast(self, query_states):
@@ -384,14 +340,10 @@ class KVQuantAttention(nn.Module):
         start = self.kcache.klen
         cos, sin = self.rotary_emb(value_states, start, start + q_len)
         query_rope = (query_states * cos) + (rotate_half(query_states) * sin)
-        sinks = self.first_few_fp16
         k = key_states[0].half().transpose(1, 2)
         v = value_states[0].half().transpose(1, 2)
-        if sinks > 0:
-            out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v, k_sink=self.kcache_fp16[0],
-                           v_sink=self.vcache_fp16[0])
-        else:
-            out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v)
+        k_sink, v_sink = self._sink_caches()
+        out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v, k_sink=k_sink, v_sink=v_sink)
         return out.to(query_states.dtype).view(bsz, q_len, self.hidden_size)
 
     def forward(self, hidden_states):

@@ -158,6 +158,15 @@ class QuantK(nn.Module):
             return None
         return self.rope.table(self.device, seq_len)
 
+    def score_table(self):
+        """table the q.K^T kernels dequantise with (the score tables are built from it): the Q-Norm one at 2 bit
+        (ML:811-815)"""
+        return self.lookup_table2 if (self.norm and self.bits == 2) else self.lookup_table
+
+    def offset_table(self):
+        """table whose two end values the outlier residuals refer to (ML:729-733): the Q-Norm one at every width"""
+        return self.lookup_table2 if self.norm else self.lookup_table
+
     def _reset_csr(self, dev):
         # uncapped-outlier CSR state (ML:402-408)
         self.rows = torch.tensor([], device=dev)
@@ -225,18 +234,18 @@ class QuantK(nn.Module):
             self.lookup_table2 = None
         self.zeropoint = ((up16 + lo16) / 2).float()
         # the two codebook values the outlier residuals refer to (ML:729-733), contiguous per channel
-        t_off = self.lookup_table2 if norm else self.lookup_table
+        t_off = self.offset_table()
         self.lut_ends = torch.stack((t_off[..., 0], t_off[..., -1]), dim=-1).reshape(-1, 2).contiguous()
         self.outlier_threshold_upper = up16.float().contiguous()
         self.outlier_threshold_lower = lo16.float().contiguous()
-        self._step_layer = None          # (cached kvq_layer of decode_kv: the tables just moved)
+        self._step_layer = None          # (layer_struct's cached kvq_layer: the tables just moved)
 
     # -- host glue kept on the GPU ------------------------------------------------
     def _outlier_rows(self, k_tok_major, resc_tok_major):
         """ML:706-751 / 928-972 for [S, C] inputs; returns (vals, idx) [S, 2*thr]."""
         n = 2 ** self.bits
         thr = _threshold_k(self.sparsity_threshold, self.hidden_size)
-        lut = (self.lookup_table2 if self.norm else self.lookup_table).reshape(-1, n)
+        lut = self.offset_table().reshape(-1, n)
         up_tmp, up_idx = torch.topk(resc_tok_major, thr, dim=-1)
         lo_tmp, lo_idx = torch.topk(resc_tok_major, thr, dim=-1, largest=False)
         up = torch.gather(k_tok_major, 1, up_idx) - lut[up_idx, n - 1]
@@ -259,8 +268,7 @@ class QuantK(nn.Module):
         pos = self.klen - self.first_few_fp16
         rope = self.rope_table(self.klen + 1)
         if self.include_sparse:
-            lut_off = self.lookup_table2 if self.norm else self.lookup_table
-            ops.append_k_fused(self.bits, self.kcache, self.lookup_table, lut_off, k,
+            ops.append_k_fused(self.bits, self.kcache, self.lookup_table, self.offset_table(), k,
                                self.outlier_threshold_lower, self.outlier_threshold_upper, self.outliers,
                                self.outlier_indices, self.num_outliers // 2, pos, self.outliers_t,
                                self.outlier_indices_t)
@@ -269,7 +277,7 @@ class QuantK(nn.Module):
         self.klen += 1
         L = self.klen - self.first_few_fp16
         mul = torch.empty((q.shape[0], q.shape[1], L), dtype=torch.float32, device=q.device)
-        table = self.lookup_table2 if (self.norm and self.bits == 2) else self.lookup_table  # ML:811-815
+        table = self.score_table()
         if self.include_sparse:
             ops.score_k(self.bits, q, self.kcache, mul, table, L, self.rope_theta, self.first_few_fp16,
                         self.outliers, self.outlier_indices, accumulate=False, rope=rope)
@@ -299,10 +307,10 @@ class QuantK(nn.Module):
             raise NotImplementedError("compact caches take the fused prefill pack only")
         if fused:
             # one launch: pack + exact top-k selection + outlier rows (+ mirror), one workgroup per token
-            lut_off = self.lookup_table2 if self.norm else self.lookup_table
-            ops.pack_k_fused(self.bits, self.kcache, self.lookup_table, lut_off, k, self.outlier_threshold_lower,
-                             self.outlier_threshold_upper, self.outliers, self.outlier_indices,
-                             self.num_outliers // 2, col0, self.outliers_t, self.outlier_indices_t)
+            ops.pack_k_fused(self.bits, self.kcache, self.lookup_table, self.offset_table(), k,
+                             self.outlier_threshold_lower, self.outlier_threshold_upper, self.outliers,
+                             self.outlier_indices, self.num_outliers // 2, col0, self.outliers_t,
+                             self.outlier_indices_t)
             self.klen += S        # (only once the library call has succeeded)
             return
         resc = torch.empty_like(k)
@@ -570,7 +578,7 @@ class QuantV(nn.Module):
         L = self.vlen - self.first_few_fp16
         mul = torch.empty((score.shape[0], score.shape[1], self.head_dim), dtype=torch.float32,
                           device=score.device)
-        table = self.lookup_table2 if (self.norm and self.bits == 2) else self.lookup_table      # ML:1237-1240
+        table = self.mix_table()
         if self.include_sparse:
             ops.mix_v(self.bits, score, self.vcache, mul, table, L, self.outliers, self.outlier_indices,
                       accumulate=False)
@@ -644,6 +652,34 @@ FUSED_ATTEND = {"1": True, "0": False}.get(os.environ.get("KVQ_FUSED_ATTEND", ""
 FUSED_ATTEND_FROM = int(os.environ.get("KVQ_FUSED_ATTEND_FROM", str(1 << 62)))
 
 
+def layer_struct(kc, vc):
+    """struct kvq_layer of a (QuantK, QuantV) pair (ops.make_layer): every pointer and option of the layer's compressed
+    cache, built on first use and kept in kc._step_layer until something it was built from changes (the key below;
+    QuantK.load_lookup_table clears the slot)."""
+    key = (id(vc), getattr(vc, "_tables_version", 0), vc.reference_tie_quirk, vc.norm, kc.norm, kc.compact, vc.compact,
+           kc.score_f16_pair, getattr(kc, "score_f32_pair", False))
+    cached = getattr(kc, "_step_layer", None)
+    if cached is None or cached[0] != key:
+        cached = (key,) + ops.make_layer(kc, vc, kc.score_table(), kc.offset_table())
+        kc._step_layer = cached
+    return cached[1]
+
+
+def _prologue(kc, vc, q, k, v, table, sinks):
+    """the multi-call paths' first launch (ops.decode_prologue): K append | V append | K score tables built from
+    `table` (kc.score_table()) (+ the sink tokens' scores) of one token; counts the token in klen / vlen and returns
+    the score workspace"""
+    ws = ops.decode_prologue(kc.bits, kc.kcache, kc.lookup_table, kc.offset_table(), k, kc.outlier_threshold_lower,
+                             kc.outlier_threshold_upper, kc.outliers, kc.outlier_indices,
+                             kc.klen - kc.first_few_fp16, vc.vcache, vc.lookup_table, vc.lut, v, vc.outliers,
+                             vc.outlier_indices, vc.vlen - vc.first_few_fp16, q, kc.num_outliers // 2, kc.outliers_t,
+                             kc.outlier_indices_t, kc.lut_ends, None if table is kc.lookup_table else table,
+                             vc.vnorm_args(), sinks)
+    kc.klen += 1
+    vc.vlen += 1
+    return ws
+
+
 def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     """One decode token through a layer's compressed KV path, GPU-resident, 5 launches:
     prologue (K append | V append | K tables) -> q.K^T (+ first softmax pass) -> softmax finish -> p.V -> slab
@@ -665,9 +701,6 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     kpos = kc.klen - kc.first_few_fp16
     vpos = vc.vlen - vc.first_few_fp16
     rope = kc.rope_table(kc.klen + 1)      # (scaled RoPE: the table of this step's position; None: the theta rule)
-    lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
-    # the score tables are built from the table the reference dequantises with: the Q-Norm one at 2 bit (ML:811-815)
-    table = kc.lookup_table2 if (kc.norm and bits == 2) else kc.lookup_table
     inv = 1.0 / (kc.head_dim ** 0.5)
     sinks = None
     if k_sink is not None:
@@ -682,32 +715,18 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     if (ONE_CALL_PER_LAYER or compact) and kpos == vpos and (sink_scores is None or sinks is not None):
         # the whole launch sequence from one library call (kvq_decode_step): the five Python / ctypes round trips of
         # the path below cost ~78 us of host time per layer, as much as the GPU needs for a 4K-token cache
-        key = (id(vc), getattr(vc, "_tables_version", 0), vc.reference_tie_quirk, vc.norm, kc.norm, kc.compact, vc.compact,
-               kc.score_f16_pair, getattr(kc, "score_f32_pair", False))
-        cached = getattr(kc, "_step_layer", None)
-        if cached is None or cached[0] != key:
-            cached = (key,) + ops.make_layer(kc, vc, table, lut_off)
-            kc._step_layer = cached
         out = torch.empty((1, H, vc.head_dim), dtype=torch.float32, device=kc.device)
         sink_probs = None if sinks is None else torch.empty_like(sink_scores)
         L = kpos + 1
         fuse = FUSE_SOFTMAX_INTO_MIX_V or L <= FUSE_SOFTMAX_UP_TO
         fused = FUSED_ATTEND if FUSED_ATTEND is not None else (bits == 4 and L >= FUSED_ATTEND_FROM)
         mode = (3 if fused else 1) if fuse else 0
-        if rope is None:
-            ops.decode_step(cached[1], kpos, q, k, v, out, mode, sinks, v_sink, sink_probs)
-        else:
-            ops.decode_step(cached[1], kpos, q, k, v, out, mode, sinks, v_sink, sink_probs, rope=rope)
+        ops.decode_step(layer_struct(kc, vc), kpos, q, k, v, out, mode, sinks, v_sink, sink_probs, rope)
         kc.klen += 1
         vc.vlen += 1
         return out, sink_probs
-    ws = ops.decode_prologue(bits, kc.kcache, kc.lookup_table, lut_off, k, kc.outlier_threshold_lower,
-                             kc.outlier_threshold_upper, kc.outliers, kc.outlier_indices, kpos, vc.vcache,
-                             vc.lookup_table, vc.lut, v, vc.outliers, vc.outlier_indices, vpos, q,
-                             kc.num_outliers // 2, kc.outliers_t, kc.outlier_indices_t, kc.lut_ends,
-                             None if table is kc.lookup_table else table, vc.vnorm_args(), sinks)
-    kc.klen += 1
-    vc.vlen += 1
+    table = kc.score_table()
+    ws = _prologue(kc, vc, q, k, v, table, sinks)
     L = kc.klen - kc.first_few_fp16
     scores = torch.empty((1, H, L), dtype=torch.float32, device=kc.device)
     out = torch.empty((1, H, vc.head_dim), dtype=torch.float32, device=kc.device)
@@ -752,9 +771,6 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     if kpos != vpos:
         raise ValueError("decode_kv (GQA): K and V caches must be in step")
     rope = kc.rope_table(kc.klen + 1)
-    lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
-    table = kc.lookup_table2 if (kc.norm and kc.bits == 2) else kc.lookup_table
-    inv = 1.0 / (kc.head_dim ** 0.5)
     v_rep = None
     if k_sink is not None:
         if sink_scores is not None or v_sink is None:
@@ -763,15 +779,9 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
         k_rep = k_sink.repeat_interleave(G, dim=0)
         sink_scores = (torch.matmul(q.half().unsqueeze(1), k_rep) / math.sqrt(kc.head_dim))[:, 0, :].contiguous()
         v_rep = v_sink.repeat_interleave(G, dim=0).contiguous()
-    key = (id(vc), getattr(vc, "_tables_version", 0), vc.reference_tie_quirk, vc.norm, kc.norm, kc.compact, vc.compact,
-           kc.score_f16_pair, getattr(kc, "score_f32_pair", False))
-    cached = getattr(kc, "_step_layer", None)
-    if cached is None or cached[0] != key:
-        cached = (key,) + ops.make_layer(kc, vc, table, lut_off)
-        kc._step_layer = cached
     out = torch.empty((1, Hq, vc.head_dim), dtype=torch.float32, device=kc.device)
     sink_probs = None if sink_scores is None else torch.empty_like(sink_scores)
-    ops.decode_step_gqa(cached[1], Hq, kpos, q, k, v, out, sink_scores, v_rep, sink_probs, rope=rope)
+    ops.decode_step_gqa(layer_struct(kc, vc), Hq, kpos, q, k, v, out, sink_scores, v_rep, sink_probs, rope=rope)
     kc.klen += 1
     vc.vlen += 1
     return out, sink_probs
@@ -808,21 +818,14 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
     rope = kc.rope_table(kc.klen + S)      # (dynamic: the table of the chunk's last position, for every column)
     kc.parallel_pack(k)
     vc.parallel_pack(v)
-    lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
-    table = kc.lookup_table2 if (kc.norm and kc.bits == 2) else kc.lookup_table
-    key = (id(vc), getattr(vc, "_tables_version", 0), vc.reference_tie_quirk, vc.norm, kc.norm, kc.compact, vc.compact,
-           kc.score_f16_pair, getattr(kc, "score_f32_pair", False))
-    cached = getattr(kc, "_step_layer", None)
-    if cached is None or cached[0] != key:
-        cached = (key,) + ops.make_layer(kc, vc, table, lut_off)
-        kc._step_layer = cached
+    layer = layer_struct(kc, vc)
     out = torch.empty((S, Hq, kc.head_dim), dtype=torch.float32, device=kc.device)
     ks = None if sinks == 0 else k_sink.contiguous()
     vs = None if sinks == 0 else v_sink.contiguous()
     # (query rows past a piece see only columns up to their own: a later piece is the same call with c0 moved on)
     for s0 in range(0, S, CHUNK_PIECE):
         n = min(CHUNK_PIECE, S - s0)
-        ops.chunk_attention(cached[1], Hq, c0 + s0, q[:, s0:s0 + n], out[s0:s0 + n], ks, vs, rope=rope)
+        ops.chunk_attention(layer, Hq, c0 + s0, q[:, s0:s0 + n], out[s0:s0 + n], ks, vs, rope=rope)
     return out
 
 
@@ -875,7 +878,7 @@ def shard_attention(kc, vc, q, k=None, v=None, pos_base=0, record=None, k_sink=N
     out = record[:H * hd].view(1, H, hd)
     stats = record[H * hd:].view(H, 2)
     inv = 1.0 / (kc.head_dim ** 0.5)
-    table = kc.lookup_table2 if (kc.norm and bits == 2) else kc.lookup_table
+    table = kc.score_table()
     pos_offset = int(pos_base)
     if k is None and kc.klen - nf == 0 and k_sink is None:
         out.zero_()
@@ -887,16 +890,7 @@ def shard_attention(kc, vc, q, k=None, v=None, pos_base=0, record=None, k_sink=N
         sink_scores = torch.empty((H, k_sink.shape[2]), dtype=torch.float16, device=kc.device)
         sinks = (k_sink, sink_scores, inv)
     if k is not None:
-        kpos = kc.klen - nf
-        vpos = vc.vlen - nf
-        lut_off = kc.lookup_table2 if kc.norm else kc.lookup_table
-        ws = ops.decode_prologue(bits, kc.kcache, kc.lookup_table, lut_off, k, kc.outlier_threshold_lower,
-                                 kc.outlier_threshold_upper, kc.outliers, kc.outlier_indices, kpos, vc.vcache,
-                                 vc.lookup_table, vc.lut, v, vc.outliers, vc.outlier_indices, vpos, q,
-                                 kc.num_outliers // 2, kc.outliers_t, kc.outlier_indices_t, kc.lut_ends,
-                                 None if table is kc.lookup_table else table, vc.vnorm_args(), sinks)
-        kc.klen += 1
-        vc.vlen += 1
+        ws = _prologue(kc, vc, q, k, v, table, sinks)
     else:
         ws = ops.score_k_tables(bits, q, table, H, sinks)
     L = kc.klen - nf
@@ -977,7 +971,6 @@ class HeadShard:
         self.v.vlen += self.first_few_fp16
         self.stage_len = stage_len
         self.device = self.k.device
-        self._layers = None
 
     def _adopt_staging(self):
         """point the staging caches' DATA buffers at the shared set (the tables stay this layer's own)"""
@@ -1019,7 +1012,6 @@ class HeadShard:
         k._step_layer = None
         # the shard's V cache keeps the sorted codebook (and, with Q-Norm, its own rows of the normalised table)
         self.v.load_lookup_table(v_quantizer, include_sparse, sparsity_threshold, norm)
-        self._layers = None
         return self
 
     def reset(self):
@@ -1048,14 +1040,7 @@ class HeadShard:
             self._extract(n)
 
     def _layer_structs(self):
-        if self._layers is None:
-            fk, fv, k, v = self.full_k, self.full_v, self.k, self.v
-            f_off = fk.lookup_table2 if fk.norm else fk.lookup_table
-            f_tab = fk.lookup_table2 if (fk.norm and self.bits == 2) else fk.lookup_table
-            s_off = k.lookup_table2 if k.norm else k.lookup_table
-            s_tab = k.lookup_table2 if (k.norm and self.bits == 2) else k.lookup_table
-            self._layers = (ops.make_layer(fk, fv, f_tab, f_off), ops.make_layer(k, v, s_tab, s_off))
-        return self._layers[0][0], self._layers[1][0]
+        return layer_struct(self.full_k, self.full_v), layer_struct(self.k, self.v)
 
     def attend(self, q, k, v, record=None, k_sink=None, v_sink=None):
         """one decode token: q [H, hd] post-RoPE query (or this shard's [n_heads, hd] slice), k / v [H * hd] the WHOLE new

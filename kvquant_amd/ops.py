@@ -191,15 +191,12 @@ def score_k(bits, q, mat, mul, lut, L, theta, pos_offset, outliers=None, outlier
     with _Dev(q):
         nbytes = _L().kvq_score_k_workspace_bytes(bits, q.shape[0], H)
         ws = _workspace(q.device, nbytes, slot="score")
-        args = (bits, _f(q, "vec"), _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), q.shape[0], H, hd,
-                int(L), max_len, float(theta), int(pos_offset),
-                None if outliers is None else _f(outliers, "outliers"),
-                None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out,
-                1 if accumulate else 0, ws.data_ptr(), ws.numel())
-        if rope is None:
-            _lib.check(_L().kvq_score_k(*args, _stream()), "kvq_score_k")
-        else:
-            _lib.check(_L().kvq_score_k_rope(*args, _rope(rope, mat.device), _stream()), "kvq_score_k_rope")
+        _lib.check(_L().kvq_score_k_rope(
+            bits, _f(q, "vec"), _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), q.shape[0], H, hd,
+            int(L), max_len, float(theta), int(pos_offset),
+            None if outliers is None else _f(outliers, "outliers"),
+            None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out,
+            1 if accumulate else 0, ws.data_ptr(), ws.numel(), _rope(rope, mat.device), _stream()), "kvq_score_k_rope")
 
 
 def outlier_mirror_rows(outliers, outlier_indices, outliers_t, outlier_indices_t, t0, t1):
@@ -285,12 +282,12 @@ def append_k_fused(bits, mat, lut, lut_off, x, lo, hi, outliers, outlier_indices
 
 def _vnorm(norm):
     """norm: None or (lut_rows2 f32 [max_len, 2^bits] or None, normscale, normoffset, zp_from_rows2,
-    reference_tie_quirk) -> kvq_vopts* / None"""
+    reference_tie_quirk) -> struct kvq_vopts (ctypes hands a const kvq_vopts * parameter its address) / None"""
     if norm is None:
         return None
     rows2, ns, no, zp2, quirk = norm
-    return ctypes.byref(_lib.VNorm(None if rows2 is None else _f(rows2, "lookup_table2"), float(ns), float(no),
-                                   1 if zp2 else 0, 1 if quirk else 0))
+    return _lib.VNorm(None if rows2 is None else _f(rows2, "lookup_table2"), float(ns), float(no),
+                      1 if zp2 else 0, 1 if quirk else 0)
 
 
 def append_v_fused(bits, mat, lut_rows, lut_sorted, x, outliers, outlier_indices, thr_k, col, norm=None):
@@ -437,6 +434,37 @@ def _act(t, name):
     return _chk(t, torch.float32, name), 0
 
 
+def _acts(q, k, v):
+    """the activations of one token, all fp16 or all fp32 -> (q ptr, k ptr, v ptr, is_half)"""
+    kp, kh = _act(k, "k")
+    vp, vh = _act(v, "v")
+    qp, qh = _act(q, "q")
+    if not (kh == vh == qh):
+        raise ValueError("q, k, v must share one dtype (fp32 or fp16)")
+    return qp, kp, vp, qh
+
+
+def _sinks(sinks, H):
+    """(k_sink f16 [H, 128, n_sink], sink_scores f16 [H, n_sink] (out), inv_sqrt_hd) -> struct kvq_sinks (ctypes hands
+    a const kvq_sinks * parameter its address), or None"""
+    if sinks is None:
+        return None
+    k_sink, sink_scores, inv = sinks
+    n_sink = sink_scores.shape[1]
+    if tuple(k_sink.shape) != (H, 128, n_sink) or sink_scores.shape[0] != H:
+        raise ValueError("sinks: k_sink [H, 128, n_sink] and sink_scores [H, n_sink] expected")
+    return _lib.Sinks(_chk(k_sink, torch.float16, "k_sink"), _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
+                      float(inv))
+
+
+def _aligned_workspace(device, nbytes, slot):
+    """_workspace with its start rounded up to 256 bytes (the one-call entries carve aligned sub-buffers out of it)
+    -> (base address, usable bytes from there, the tensor that owns them)"""
+    ws = _workspace(device, nbytes + 256, slot=slot)
+    base = (ws.data_ptr() + 255) & ~255
+    return base, ws.numel() - (base - ws.data_ptr()), ws
+
+
 def decode_prologue(bits, kmat, klut, klut_off, k, lo, hi, koutl, kidx, kcol, vmat, vlut_rows, vlut_sorted, v,
                     voutl, vidx, vcol, q, thr_k, koutl_t=None, kidx_t=None, klut_ends=None, klut_score=None,
                     vnorm=None, sinks=None):
@@ -445,19 +473,8 @@ def decode_prologue(bits, kmat, klut, klut_off, k, lo, hi, koutl, kidx, kcol, vm
     (default klut).  sinks = (k_sink f16 [H, 128, n_sink], sink_scores f16 [H, n_sink] (out), inv_sqrt_hd): the head
     workgroups also write the scaled scores of the fp16 sink tokens.  Returns the score workspace tensor."""
     H, hd, max_len = _cache_dims(kmat, bits)
-    sk = None
-    if sinks is not None:
-        k_sink, sink_scores, inv = sinks
-        n_sink = sink_scores.shape[1]
-        if tuple(k_sink.shape) != (H, 128, n_sink) or sink_scores.shape[0] != H:
-            raise ValueError("sinks: k_sink [H, 128, n_sink] and sink_scores [H, n_sink] expected")
-        sk = _lib.Sinks(_chk(k_sink, torch.float16, "k_sink"), _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
-                        float(inv))
-    kp, kh = _act(k, "k")
-    vp, vh = _act(v, "v")
-    qp, qh = _act(q, "q")
-    if not (kh == vh == qh):
-        raise ValueError("q, k, v must share one dtype (fp32 or fp16)")
+    sk = _sinks(sinks, H)
+    qp, kp, vp, kh = _acts(q, k, v)
     with _Dev(kmat):
         nbytes = _L().kvq_score_k_workspace_bytes(bits, 1, H)
         ws = _workspace(kmat.device, nbytes, slot="score")
@@ -467,8 +484,8 @@ def decode_prologue(bits, kmat, klut, klut_off, k, lo, hi, koutl, kidx, kcol, vm
             _f(vlut_rows, "lookup_table"), _f(vlut_sorted, "lut"), vp, _f(voutl, "outliers"),
             _i(vidx, "outlier_indices"), int(vcol), qp, kh, int(thr_k), H, hd, max_len,
             *_mirror(koutl_t, kidx_t, thr_k, max_len), None if klut_ends is None else _f(klut_ends, "lut_ends"),
-            None if klut_score is None else _f(klut_score, "lut_score"), _vnorm(vnorm),
-            None if sk is None else ctypes.byref(sk), ws.data_ptr(), ws.numel(), _stream()), "kvq_decode_prologue")
+            None if klut_score is None else _f(klut_score, "lut_score"), _vnorm(vnorm), sk, ws.data_ptr(),
+            ws.numel(), _stream()), "kvq_decode_prologue")
     return ws
 
 
@@ -478,15 +495,11 @@ def score_k_prepared(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers=Non
     H, hd, max_len = _cache_dims(mat, bits)
     n_out = 0 if outliers is None else outliers.shape[1]
     with _Dev(mat):
-        args = (bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
-                int(pos_offset), None if outliers is None else _f(outliers, "outliers"),
-                None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out, 1 if accumulate else 0,
-                ws.data_ptr(), ws.numel())
-        if rope is None:
-            _lib.check(_L().kvq_score_k_prepared(*args, _stream()), "kvq_score_k_prepared")
-        else:
-            _lib.check(_L().kvq_score_k_prepared_rope(*args, _rope(rope, mat.device), _stream()),
-                       "kvq_score_k_prepared_rope")
+        _lib.check(_L().kvq_score_k_prepared_rope(
+            bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
+            int(pos_offset), None if outliers is None else _f(outliers, "outliers"),
+            None if outliers is None else _i(outlier_indices, "outlier_indices"), n_out, 1 if accumulate else 0,
+            ws.data_ptr(), ws.numel(), _rope(rope, mat.device), _stream()), "kvq_score_k_prepared_rope")
 
 
 def score_k_prepared_softmax(bits, mat, mul, lut, L, theta, pos_offset, ws, outliers, outlier_indices, inv_sqrt_hd,
@@ -497,16 +510,13 @@ def score_k_prepared_softmax(bits, mat, mul, lut, L, theta, pos_offset, ws, outl
     H, hd, max_len = _cache_dims(mat, bits)
     with _Dev(mat):
         parts = _workspace(mat.device, H * n_parts * 8, slot="softmax")
-        args = (bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
-                int(pos_offset), _f(outliers, "outliers"), _i(outlier_indices, "outlier_indices"), outliers.shape[1],
-                *_mirror(outliers_t, outlier_indices_t, outliers.shape[1] // 2, max_len),
-                ws.data_ptr(), ws.numel(), float(inv_sqrt_hd), parts.data_ptr(), n_parts,
-                _lib.SCORE_F16_PAIR_TABLES if f16_pair else 0)
-        if rope is None:
-            _lib.check(_L().kvq_score_k_prepared_softmax_ex(*args, _stream()), "kvq_score_k_prepared_softmax_ex")
-        else:
-            _lib.check(_L().kvq_score_k_prepared_softmax_rope(*args, _rope(rope, mat.device), _stream()),
-                       "kvq_score_k_prepared_softmax_rope")
+        _lib.check(_L().kvq_score_k_prepared_softmax_rope(
+            bits, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lookup_table"), H, hd, int(L), max_len, float(theta),
+            int(pos_offset), _f(outliers, "outliers"), _i(outlier_indices, "outlier_indices"), outliers.shape[1],
+            *_mirror(outliers_t, outlier_indices_t, outliers.shape[1] // 2, max_len),
+            ws.data_ptr(), ws.numel(), float(inv_sqrt_hd), parts.data_ptr(), n_parts,
+            _lib.SCORE_F16_PAIR_TABLES if f16_pair else 0, _rope(rope, mat.device), _stream()),
+            "kvq_score_k_prepared_softmax_rope")
     return parts
 
 
@@ -587,36 +597,23 @@ def mix_v_softmax(bits, scores, parts, n_parts, inv_sqrt_hd, mat, mul, lut_rows,
             None if n_sink == 0 else _chk(sink_scores, torch.float16, "sink_scores"),
             None if n_sink == 0 else sink_probs.data_ptr(), n_sink,
             None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
-            None if probs is None else probs.data_ptr(),
-            _i(mat, "mat"), _f(mul, "mul"), _f(lut_rows, "lookup_table"), H, hd, int(L), max_len,
+            probs.data_ptr(), _i(mat, "mat"), _f(mul, "mul"), _f(lut_rows, "lookup_table"), H, hd, int(L), max_len,
             _fo(outliers, "outliers"), _i(outlier_indices, "outlier_indices"), outlier_indices.shape[1], 0,
             wsv.data_ptr(), wsv.numel(), _stream()), "kvq_mix_v_softmax")
     return sink_probs
 
 
 # ---- token-sharded single stream ---------------------------------------------------------------------------------
-def _sinks_struct(sinks, H):
-    """(k_sink f16 [H, 128, n_sink], sink_scores f16 [H, n_sink] (out), inv_sqrt_hd) -> struct kvq_sinks, or None"""
-    if sinks is None:
-        return None
-    k_sink, sink_scores, inv = sinks
-    n_sink = sink_scores.shape[1]
-    if tuple(k_sink.shape) != (H, 128, n_sink) or sink_scores.shape[0] != H:
-        raise ValueError("sinks: k_sink [H, 128, n_sink] and sink_scores [H, n_sink] expected")
-    return _lib.Sinks(_chk(k_sink, torch.float16, "k_sink"), _chk(sink_scores, torch.float16, "sink_scores"), n_sink, float(inv))
-
-
 def score_k_tables(bits, q, lut, H, sinks=None):
     """query-premultiplied K tables into the score workspace without an append (kvq_score_k_tables); returns the
     workspace tensor for score_k_prepared[_softmax].  sinks = (k_sink, sink_scores (out), inv_sqrt_hd): the scaled
     scores of the fp16 sink tokens this shard holds are written too."""
     qp, qh = _act(q, "q")
-    sk = _sinks_struct(sinks, H)
+    sk = _sinks(sinks, H)
     with _Dev(lut):
         nbytes = _L().kvq_score_k_workspace_bytes(bits, 1, H)
         ws = _workspace(lut.device, nbytes, slot="score")
-        _lib.check(_L().kvq_score_k_tables(bits, qp, qh, _f(lut, "lookup_table"), H, 128,
-                                           None if sk is None else ctypes.byref(sk), ws.data_ptr(), ws.numel(),
+        _lib.check(_L().kvq_score_k_tables(bits, qp, qh, _f(lut, "lookup_table"), H, 128, sk, ws.data_ptr(), ws.numel(),
                                            _stream()), "kvq_score_k_tables")
     return ws
 
@@ -681,12 +678,7 @@ def make_layer(kc, vc, table, lut_off):
     thr_k = kc.num_outliers // 2
     if _mirror(kc.outliers_t, kc.outlier_indices_t, thr_k, max_len)[1] is None:
         raise ValueError("decode_step needs the token-contiguous outlier mirror")
-    vn = vc.vnorm_args()
-    vstruct = None
-    if vn is not None:
-        rows2, ns, no, zp2, quirk = vn
-        vstruct = _lib.VNorm(None if rows2 is None else _f(rows2, "lookup_table2"), float(ns), float(no), 1 if zp2 else 0,
-                             1 if quirk else 0)
+    vstruct = _vnorm(vc.vnorm_args())
     mix = vc.mix_table()
     ly = _lib.Layer(
         kc.bits, H, hd, thr_k, max_len, float(kc.rope_theta), int(kc.first_few_fp16),
@@ -707,73 +699,58 @@ def decode_step(layer, col, q, k, v, out, fuse_softmax, sinks=None, v_sink=None,
     from make_layer; col: append column (cached tokens before this one, sink tokens not counted); q [H, 128], k, v
     [C]: all fp16 or all fp32; out f32 [1, H, hd].  sinks = (k_sink, sink_scores (out), inv_sqrt_hd) with v_sink /
     sink_probs, or None."""
-    kp, kh = _act(k, "k")
-    vp, vh = _act(v, "v")
-    qp, qh = _act(q, "q")
-    if not (kh == vh == qh):
-        raise ValueError("q, k, v must share one dtype (fp32 or fp16)")
-    sk = None
-    if sinks is not None:
-        k_sink, sink_scores, inv = sinks
-        sk = _lib.Sinks(_chk(k_sink, torch.float16, "k_sink"), _chk(sink_scores, torch.float16, "sink_scores"),
-                        sink_scores.shape[1], float(inv))
+    qp, kp, vp, kh = _acts(q, k, v)
+    sk = _sinks(sinks, layer.H)
     with _Dev(out):
         nbytes = _L().kvq_decode_step_workspace_bytes(layer.bits, layer.H, layer.hd, int(col) + 1)
-        ws = _workspace(out.device, nbytes + 256, slot="step")
-        base = (ws.data_ptr() + 255) & ~255
-        args = (ctypes.byref(layer), int(col), int(col), qp, kp, vp, kh, None if sk is None else ctypes.byref(sk),
-                None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
-                None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax),
-                base, ws.numel() - (base - ws.data_ptr()))
-        if rope is None:
-            _lib.check(_L().kvq_decode_step(*args, _stream()), "kvq_decode_step")
-        else:
-            _lib.check(_L().kvq_decode_step_rope(*args, _rope(rope, out.device), _stream()), "kvq_decode_step_rope")
+        base, usable, ws = _aligned_workspace(out.device, nbytes, "step")
+        _lib.check(_L().kvq_decode_step_rope(
+            ctypes.byref(layer), int(col), int(col), qp, kp, vp, kh, sk,
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
+            None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax),
+            base, usable, _rope(rope, out.device), _stream()), "kvq_decode_step_rope")
 
 
 # ---- prefill attention on the matrix cores ----------------------------------------------------------------------
 def prefill_attention(q, k, v, softmax_scale=None):
-    """causal attention of a prompt: q, k, v fp16 [H, S, 128] views (any strides with a contiguous last dimension,
-    e.g. transposes of [S, H, 128]) -> fp16 [S, H*128] (token-major, ready for o_proj)."""
+    """causal attention of a prompt: q fp16 [Hq, S, 128], k, v fp16 [Hkv, S, 128] views (any strides with a contiguous
+    last dimension, e.g. transposes of [S, H, 128]); Hq = G * Hkv, 1 <= G <= 8, query head h attends with KV head
+    h // G (kvq_prefill_attention for Hq = Hkv, kvq_prefill_attention_gqa otherwise).
+    -> fp16 [S, Hq*128] (token-major, ready for o_proj)."""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(2) == 1):
             raise ValueError("%s: expected an fp16 GPU tensor [H, S, head_dim] with a contiguous last dimension" % name)
-    H, S, hd = q.shape
-    if k.shape != q.shape or v.shape != q.shape:
-        raise ValueError("q, k, v must have the same shape")
-    out = torch.empty((S, H, hd), dtype=torch.float16, device=q.device)
+    Hq, S, hd = q.shape
+    Hkv = k.shape[0]
+    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or Hkv <= 0 or Hq % Hkv or not 1 <= Hq // Hkv <= 8:
+        raise ValueError("prefill_attention: q [Hq, S, hd], k / v [Hkv, S, hd] with Hq = G * Hkv, 1 <= G <= 8")
+    out = torch.empty((S, Hq, hd), dtype=torch.float16, device=q.device)
     scale = float(softmax_scale) if softmax_scale is not None else 1.0 / (hd ** 0.5)
+    strides = (q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(1), out.stride(0))
     with _Dev(q):
-        _lib.check(_L().kvq_prefill_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), H, S, hd,
-                                             q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
-                                             v.stride(1), out.stride(1), out.stride(0), scale, _stream()),
-                   "kvq_prefill_attention")
-    return out.view(S, H * hd)
-
-
-def _step_ws(dev, bits, H, hd, L):
-    nbytes = _L().kvq_decode_step_workspace_bytes(bits, H, hd, int(L))
-    ws = _workspace(dev, nbytes + 256, slot="step")
-    return (ws.data_ptr() + 255) & ~255, ws.numel() - 256, ws
+        if Hq == Hkv:
+            _lib.check(_L().kvq_prefill_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), Hq, S, hd,
+                                                 *strides, scale, _stream()), "kvq_prefill_attention")
+        else:
+            _lib.check(_L().kvq_prefill_attention_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), Hq, Hkv,
+                                                     S, hd, *strides, scale, _stream()), "kvq_prefill_attention_gqa")
+    return out.view(S, Hq * hd)
 
 
 def head_shard_step(full_layer, shard_layer, h0, col, q, k, v, out, fuse_softmax, sinks=None, v_sink=None, sink_probs=None):
     """kvq_head_shard_step: whole-token append into the staging cache -> extract of the shard's heads -> the shard's
     attention, ONE library call.  q [n_heads, 128] (the shard's heads), k, v [C] (the whole token): all fp16 or all fp32;
     out f32 [1, n_heads, hd]; sinks = (k_sink, sink_scores (out), inv_sqrt_hd) of the shard's heads."""
-    kp, kh = _act(k, "k")
-    vp, vh = _act(v, "v")
-    qp, qh = _act(q, "q")
-    if not (kh == vh == qh):
-        raise ValueError("q, k, v must share one dtype (fp32 or fp16)")
-    sk = _sinks_struct(sinks, shard_layer.H)
+    qp, kp, vp, kh = _acts(q, k, v)
+    sk = _sinks(sinks, shard_layer.H)
     with _Dev(out):
-        base, nb, keep = _step_ws(out.device, shard_layer.bits, shard_layer.H, shard_layer.hd, int(col) + 1)
+        nbytes = _L().kvq_decode_step_workspace_bytes(shard_layer.bits, shard_layer.H, shard_layer.hd, int(col) + 1)
+        base, usable, ws = _aligned_workspace(out.device, nbytes, "step")
         _lib.check(_L().kvq_head_shard_step(
-            ctypes.byref(full_layer), ctypes.byref(shard_layer), int(h0), int(col), qp, kp, vp, kh,
-            None if sk is None else ctypes.byref(sk), None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
-            None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax), base, nb, _stream()),
-            "kvq_head_shard_step")
+            ctypes.byref(full_layer), ctypes.byref(shard_layer), int(h0), int(col), qp, kp, vp, kh, sk,
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
+            None if sink_probs is None else sink_probs.data_ptr(), _f(out, "out"), int(fuse_softmax), base, usable,
+            _stream()), "kvq_head_shard_step")
 
 
 # ---- grouped-query attention (GQA): Hq query heads over Hkv KV heads, query head h reads KV head h // G -------------
@@ -796,15 +773,12 @@ def score_k_gqa(bits, q, mat, mul, lut, L, theta, pos_offset, outliers_t=None, o
         if nbytes == 0:
             raise ValueError("score_k_gqa: unsupported shape (Hq=%d, Hkv=%d, bits=%d)" % (Hq, Hkv, bits))
         ws = _workspace(mul.device, nbytes, slot="gqa_score")
-        args = (bits, qp, qh, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lut"), Hq, Hkv, hd, int(L), max_len, float(theta),
-                int(pos_offset), _fo(outliers_t, "outliers_t"), _io(outlier_indices_t, "outlier_indices_t"), n_out,
-                float(inv_sqrt_hd if inv_sqrt_hd is not None else 1.0 / hd ** 0.5),
-                None if parts is None else _f(parts, "parts"), 0 if parts is None else parts.shape[1],
-                ws.data_ptr(), ws.numel())
-        if rope is None:
-            _lib.check(_L().kvq_score_k_gqa(*args, _stream()), "kvq_score_k_gqa")
-        else:
-            _lib.check(_L().kvq_score_k_gqa_rope(*args, _rope(rope, mul.device), _stream()), "kvq_score_k_gqa_rope")
+        _lib.check(_L().kvq_score_k_gqa_rope(
+            bits, qp, qh, _i(mat, "mat"), _f(mul, "mul"), _f(lut, "lut"), Hq, Hkv, hd, int(L), max_len, float(theta),
+            int(pos_offset), _fo(outliers_t, "outliers_t"), _io(outlier_indices_t, "outlier_indices_t"), n_out,
+            float(inv_sqrt_hd if inv_sqrt_hd is not None else 1.0 / hd ** 0.5),
+            None if parts is None else _f(parts, "parts"), 0 if parts is None else parts.shape[1],
+            ws.data_ptr(), ws.numel(), _rope(rope, mul.device), _stream()), "kvq_score_k_gqa_rope")
     return mul
 
 
@@ -834,49 +808,19 @@ def decode_step_gqa(layer, Hq, col, q, k, v, out, sink_scores=None, v_sink=None,
     layer: struct from make_layer (layer.H = KV heads); q [Hq, 128], k, v [Hkv*128]: all fp16 or all fp32; out f32
     [1, Hq, hd].  sink_scores: fp16 [Hq, n_sink] already scaled (sink_probs receives their probabilities);
     v_sink: fp16 [Hq, n_sink, 128], then out also holds the sink tokens' share."""
-    kp, kh = _act(k, "k")
-    vp, vh = _act(v, "v")
-    qp, qh = _act(q, "q")
-    if not (kh == vh == qh):
-        raise ValueError("q, k, v must share one dtype (fp32 or fp16)")
+    qp, kp, vp, kh = _acts(q, k, v)
     n_sink = 0 if sink_scores is None else sink_scores.shape[1]
     with _Dev(out):
         nbytes = _L().kvq_decode_step_gqa_workspace_bytes(layer.bits, int(Hq), layer.H, layer.hd, int(col) + 1)
         if nbytes == 0:
             raise ValueError("decode_step_gqa: unsupported shape (Hq=%d, Hkv=%d)" % (Hq, layer.H))
-        ws = _workspace(out.device, nbytes + 256, slot="step")
-        base = (ws.data_ptr() + 255) & ~255
-        args = (ctypes.byref(layer), int(Hq), int(col), qp, kp, vp, kh,
-                None if sink_scores is None else _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
-                None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
-                None if sink_probs is None else _chk(sink_probs, torch.float16, "sink_probs"), _f(out, "out"),
-                base, ws.numel() - (base - ws.data_ptr()))
-        if rope is None:
-            _lib.check(_L().kvq_decode_step_gqa(*args, _stream()), "kvq_decode_step_gqa")
-        else:
-            _lib.check(_L().kvq_decode_step_gqa_rope(*args, _rope(rope, out.device), _stream()),
-                       "kvq_decode_step_gqa_rope")
-
-
-def prefill_attention_gqa(q, k, v, softmax_scale=None):
-    """causal attention of a prompt with grouped KV heads: q fp16 [Hq, S, 128], k, v fp16 [Hkv, S, 128] views (any
-    strides with a contiguous last dimension); query head h attends with KV head h // (Hq / Hkv).
-    -> fp16 [S, Hq*128] (token-major, ready for o_proj)."""
-    for t, name in ((q, "q"), (k, "k"), (v, "v")):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float16 and t.dim() == 3 and t.stride(2) == 1):
-            raise ValueError("%s: expected an fp16 GPU tensor [H, S, head_dim] with a contiguous last dimension" % name)
-    Hq, S, hd = q.shape
-    Hkv = k.shape[0]
-    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or Hkv <= 0 or Hq % Hkv or not 1 <= Hq // Hkv <= 8:
-        raise ValueError("prefill_attention_gqa: q [Hq, S, hd], k / v [Hkv, S, hd] with Hq = G * Hkv, 1 <= G <= 8")
-    out = torch.empty((S, Hq, hd), dtype=torch.float16, device=q.device)
-    scale = float(softmax_scale) if softmax_scale is not None else 1.0 / (hd ** 0.5)
-    with _Dev(q):
-        _lib.check(_L().kvq_prefill_attention_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), Hq, Hkv, S,
-                                                 hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0),
-                                                 v.stride(1), out.stride(1), out.stride(0), scale, _stream()),
-                   "kvq_prefill_attention_gqa")
-    return out.view(S, Hq * hd)
+        base, usable, ws = _aligned_workspace(out.device, nbytes, "step")
+        _lib.check(_L().kvq_decode_step_gqa_rope(
+            ctypes.byref(layer), int(Hq), int(col), qp, kp, vp, kh,
+            None if sink_scores is None else _chk(sink_scores, torch.float16, "sink_scores"), n_sink,
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"),
+            None if sink_probs is None else _chk(sink_probs, torch.float16, "sink_probs"), _f(out, "out"),
+            base, usable, _rope(rope, out.device), _stream()), "kvq_decode_step_gqa_rope")
 
 
 # ---- a chunk of S new tokens over the compressed cache (MFMA flash kernel, kvq_chunk_attn.hip) ---------------------
@@ -916,14 +860,10 @@ def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=N
         nbytes = getattr(_L(), name + "_workspace_bytes")(int(Hq), layer.H, int(S), int(c0))
         if nbytes == 0:
             raise ValueError("chunk_attention: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
-        ws = _workspace(out.device, nbytes + 256, slot="chunk")
-        base = (ws.data_ptr() + 255) & ~255
-        args = (ctypes.byref(layer), int(Hq), int(S), int(c0), q.data_ptr(), q.stride(0), q.stride(1),
-                None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
-                None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
-                base, ws.numel() - (base - ws.data_ptr()))
-        if rope is None:
-            _lib.check(getattr(_L(), name)(*args, _stream()), name)
-        else:
-            _lib.check(getattr(_L(), name + "_rope")(*args, _rope(rope, out.device), _stream()), name + "_rope")
+        base, usable, ws = _aligned_workspace(out.device, nbytes, "chunk")
+        _lib.check(getattr(_L(), name + "_rope")(
+            ctypes.byref(layer), int(Hq), int(S), int(c0), q.data_ptr(), q.stride(0), q.stride(1),
+            None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
+            base, usable, _rope(rope, out.device), _stream()), name + "_rope")
     return out

@@ -1,6 +1,7 @@
 """Chunk attention, host side (no GPU): the entry points exist, the workspace size is a function of the shape, every bad
 argument is refused before any launch, and KVQuantAttention routes q_len > 1 on a warm cache as documented."""
 import ctypes
+import math
 
 import pytest
 import torch
@@ -101,8 +102,9 @@ class _Rec:
         self.calls = []
 
 
-def _attention(monkeypatch, rec, sinks=0, G=1, **kw):
-    """a CPU KVQuantAttention whose compressed-cache calls are stubs that record what they were given"""
+def _attention(monkeypatch, rec, sinks=0, G=1, stub_tokens=True, **kw):
+    """a CPU KVQuantAttention whose compressed-cache calls are stubs that record what they were given (stub_tokens:
+    q_len == 1 calls of attend() too)"""
     from kvquant_amd import attention as at
     a = at.KVQuantAttention(hidden_size=512 * G, num_heads=4 * G, num_key_value_heads=4, abits=4, first_few_fp16=sinks,
                             maxseqlen=256, device="cpu", make_proj=False, **kw)
@@ -115,6 +117,8 @@ def _attention(monkeypatch, rec, sinks=0, G=1, **kw):
         vc.vlen += S
         return torch.zeros(S, q.shape[0], 128)
     monkeypatch.setattr(at, "chunk_kv", fake_chunk)
+    if not stub_tokens:
+        return a
     orig = at.KVQuantAttention.attend
 
     def attend(self, q, k, v):
@@ -157,3 +161,94 @@ def test_attend_fallbacks(monkeypatch, knob):
     a.kcache.klen = a.vcache.vlen = 10
     a.attend_multi(*_qkv(a, 4, torch.float32 if knob == "fp32" else torch.float16))
     assert rec.calls == [("token", 10), ("token", 11), ("token", 12), ("token", 13)]
+
+
+def _randn_qkv(a, n, gen):
+    H, Hkv = a.num_heads, a.num_key_value_heads
+    return (torch.randn(1, H, n, 128, generator=gen).half(), torch.randn(1, Hkv, n, 128, generator=gen).half(),
+            torch.randn(1, Hkv, n, 128, generator=gen).half())
+
+
+@pytest.mark.parametrize("G", [1, 4])
+def test_sink_filling_phase(monkeypatch, G):
+    """five single tokens into an empty cache with 5 fp16 sink tokens: every output bit-equal to the plain statement
+    of the phase (post-RoPE keys, KV heads repeated per group, fp16 matmuls around an fp32 softmax rounded to fp16)"""
+    from kvquant_amd.attention import rotate_half
+    a = _attention(monkeypatch, _Rec(), sinks=5, G=G, stub_tokens=False)
+    gen = torch.Generator().manual_seed(100 + G)
+    keys = torch.zeros(1, 4, 128, 0, dtype=torch.float16)
+    vals = torch.zeros(1, 4, 0, 128, dtype=torch.float16)
+    for t in range(5):
+        q, k, v = _randn_qkv(a, 1, gen)
+        out = a.attend(q, k, v)
+        cos, sin = a.rotary_emb(v, t, t + 1)
+        q_rope = q * cos + rotate_half(q) * sin
+        k_rope = k * cos + rotate_half(k) * sin
+        keys = torch.cat((keys, k_rope.transpose(2, 3)), dim=3)
+        vals = torch.cat((vals, v), dim=2)
+        w = torch.matmul(q_rope, keys.repeat_interleave(G, dim=1)) / math.sqrt(128)
+        w = torch.softmax(w, dim=-1, dtype=torch.float32).half()
+        ref = torch.matmul(w, vals.repeat_interleave(G, dim=1)).transpose(1, 2).reshape(1, 1, 512 * G)
+        assert out.dtype == torch.float16 and torch.equal(out, ref), t
+    assert a.kcache.klen == 5 and a.vcache.vlen == 5
+
+
+@pytest.mark.parametrize("sinks", [0, 5])
+@pytest.mark.parametrize("G", [1, 4])
+def test_prefill_and_decode_routing(monkeypatch, G, sinks):
+    """a 7-token prompt goes through ONE ops.prefill_attention call and the packs of the tokens behind the fp16 sink
+    tokens; a decode token through ONE decode_kv call that gets the sink caches exactly when there are sink tokens"""
+    from kvquant_amd import attention as at
+    from kvquant_amd.cache import QuantK, QuantV
+    a = _attention(monkeypatch, _Rec(), sinks=sinks, G=G, stub_tokens=False)
+    prefills, packs, decodes = [], [], []
+
+    def fake_prefill(q, k, v, softmax_scale=None):
+        prefills.append((tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+        return torch.zeros(q.shape[1], q.shape[0] * 128, dtype=torch.float16)
+
+    def fake_pack_k(self, k, *args, **kw):
+        packs.append(("k", tuple(k.shape)))
+        self.klen += k.shape[-1]
+
+    def fake_pack_v(self, v, *args, **kw):
+        packs.append(("v", tuple(v.shape)))
+        self.vlen += v.shape[-1]
+
+    def fake_decode(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
+        decodes.append((tuple(q.shape), sink_scores, k_sink, v_sink))
+        return torch.zeros(1, q.shape[0], 128), None
+    monkeypatch.setattr(at.ops, "prefill_attention", fake_prefill)
+    monkeypatch.setattr(QuantK, "parallel_pack", fake_pack_k)
+    monkeypatch.setattr(QuantV, "parallel_pack", fake_pack_v)
+    monkeypatch.setattr(at.ops, "rope_q_f16", lambda q, cos, sin: q)
+    monkeypatch.setattr(at, "decode_kv", fake_decode)
+
+    q, k, v = _randn_qkv(a, 7, torch.Generator().manual_seed(200 + G))
+    out = a.attend(q, k, v)
+    assert out.shape == (1, 7, 512 * G)
+    assert prefills == [((4 * G, 7, 128), (4, 7, 128), (4, 7, 128))]
+    if sinks:
+        cos, sin = a.rotary_emb(v, 0, 7)
+        k_rope = k * cos + at.rotate_half(k) * sin
+        assert torch.equal(a.kcache_fp16, k_rope[:, :, :5].transpose(2, 3))
+        assert torch.equal(a.vcache_fp16, v[:, :, :5])
+        assert packs == [("k", (4, 128, 2)), ("v", (4, 128, 2))]
+    else:
+        assert packs == [("k", (4, 128, 7)), ("v", (4, 128, 7))]
+    assert a.kcache.klen == 7 and a.vcache.vlen == 7
+
+    tok = _randn_qkv(a, 1, torch.Generator().manual_seed(300 + G))
+    out = a.attend(*tok)
+    assert out.shape == (1, 1, 512 * G)
+    assert len(decodes) == 1
+    q_shape, sink_scores, k_sink, v_sink = decodes[0]
+    assert q_shape == (4 * G, 128) and sink_scores is None
+    assert (k_sink is not None) == (sinks > 0) and (v_sink is not None) == (sinks > 0)
+    if sinks:
+        assert k_sink.shape == (4, 128, 5) and v_sink.shape == (4, 5, 128)
+    if G > 1:
+        a.kcache.include_sparse = False
+        with pytest.raises(ValueError):
+            a.attend(*tok)
+        assert len(decodes) == 1

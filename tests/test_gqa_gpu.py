@@ -109,7 +109,7 @@ def test_prefill_attention_gqa(Hq, Hkv, S):
     q = torch.randn(Hq, S, 128, generator=g, device=DEV).half()
     k = torch.randn(Hkv, S, 128, generator=g, device=DEV).half()
     v = torch.randn(Hkv, S, 128, generator=g, device=DEV).half()
-    out = ops.prefill_attention_gqa(q, k, v).view(S, Hq, 128).transpose(0, 1).float()
+    out = ops.prefill_attention(q, k, v).view(S, Hq, 128).transpose(0, 1).float()
     G = Hq // Hkv
     kr, vr = k.float().repeat_interleave(G, 0), v.float().repeat_interleave(G, 0)
     s = torch.matmul(q.float(), kr.transpose(1, 2)) / math.sqrt(128)

@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from kvquant_amd import ops  # noqa: E402
-from kvquant_amd.cache import chunk_kv, decode_kv  # noqa: E402
+from kvquant_amd.cache import chunk_kv, decode_kv, layer_struct  # noqa: E402
 from tests import chunk_check as cc  # noqa: E402
 
 PEAK = 2.5e15
@@ -75,7 +75,7 @@ def main():
                     kc.klen = vc.vlen = L0
                     chunk_kv(kc, vc, q, k, v)
                 t_chunk = timed(chunk, args.reps)
-                layer = kc._step_layer[1]
+                layer = layer_struct(kc, vc)
 
                 def attn_only():
                     ops.chunk_attention(layer, Hq, L0, q)

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from kvquant_amd import ops  # noqa: E402
-from kvquant_amd.cache import chunk_kv, decode_kv  # noqa: E402
+from kvquant_amd.cache import chunk_kv, decode_kv, layer_struct  # noqa: E402
 from tests import chunk_check as cc  # noqa: E402
 
 
@@ -73,7 +73,7 @@ def main():
                         chunk_kv(kc, vc, q, k, v)
                     return run
                 verify(True)()
-                layer = kc._step_layer[1]
+                layer = layer_struct(kc, vc)
 
                 def attn(grouped):
                     def run():
