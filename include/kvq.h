@@ -82,6 +82,9 @@ extern "C" {
  *        Later in 403: kvq_chunk_attention_grouped[_rope, _workspace_bytes]: the chunk attention for G >= 2 and S <= 32
  *        (draft verification) with the K / V tile decoded once per KV head.  Additive only, kvq_version() stays 403;
  *        kvq_chunk_attention[_rope] keeps its kernels and its results bit for bit.
+ *        Later in 403: kvq_chunk_attention_tree[_rope, _workspace_bytes] (draft trees: a tree mask and per-node
+ *        positions on the grouped kernel) and kvq_keep_columns (the accepted path moves into contiguous columns).
+ *        Additive only, kvq_version() stays 403; the existing chunk kernels are unchanged.
  *        A binding checks `kvq_version() / 100 == KVQ_ABI_MAJOR`. */
 #define KVQ_ABI_MAJOR 4
 KVQ_API int kvq_version(void);
@@ -682,6 +685,43 @@ KVQ_API int kvq_chunk_attention_grouped_rope(const kvq_layer *layer, int Hq, int
                                              int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
                                              const uint16_t *v_sink, int n_sink, float *out, void *workspace,
                                              size_t workspace_bytes, const kvq_rope *rope, void *stream);
+
+/* ---- draft TREES (SpecInfer / Medusa-style verification) and the accepted path --------------------------------------
+ * kvq_chunk_attention_tree[_rope]: kvq_chunk_attention_grouped[_rope] with a tree mask and per-node positions.  The chunk
+ * of 2 <= S <= 32 rows is a tree in topological order: row 0 is the root (the last real token), row i >= 1 a draft node
+ * whose parent is row parent[i] < i.  With depth[0] = 0, depth[i] = depth[parent[i]] + 1:
+ *   - query i (RoPE'd by the caller at position layer->pos_offset + c0 + depth[i]) attends to the sink tokens, to every
+ *     compressed column < c0, and to column c0 + j iff j == i or node j is an ancestor of i;
+ *   - column c0 + j is rotated at position layer->pos_offset + c0 + depth[j] (siblings share a position); columns < c0
+ *     at their own, as everywhere else.
+ * The chunk's K / V are packed into columns c0 .. c0+S-1 in row order as for kvq_chunk_attention (the packs do not
+ * depend on the position).  parent: HOST memory, S entries, parent[0] is ignored -- the host derives the depths and the
+ * ancestor sets and passes them in the kernel arguments (no device allocation, no copy), so the array may be reused as
+ * soon as the call returns.  Grouped geometry for every 1 <= G <= 8 (G = 1: one wave of the workgroup holds rows).
+ * KVQ_EINVAL before any launch: parent == NULL, parent[i] >= i, S < 2, S > 32 and everything kvq_chunk_attention
+ * refuses; kvq_chunk_attention_tree_workspace_bytes is 0 for the same shapes.  The chain parent[i] = i - 1 gives
+ * kvq_chunk_attention_grouped's output bit for bit.  Additive only, kvq_version() stays 403. */
+KVQ_API size_t kvq_chunk_attention_tree_workspace_bytes(int Hq, int Hkv, int S, int64_t c0);
+KVQ_API int kvq_chunk_attention_tree(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q,
+                                     int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                     const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                     size_t workspace_bytes, const uint8_t *parent /* HOST */, void *stream);
+KVQ_API int kvq_chunk_attention_tree_rope(const kvq_layer *layer, int Hq, int S, int64_t c0, const void *q,
+                                          int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                          const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                          size_t workspace_bytes, const uint8_t *parent /* HOST */, const kvq_rope *rope,
+                                          void *stream);
+/* Keep n_keep of the S newest compressed columns c0 .. c0+S-1 (the accepted root-to-leaf path of a tree round): column
+ * c0 + keep[j] moves to c0 + j in every array in which a column owns storage -- K: kmat, koutliers / kidx and the mirror
+ * koutliers_t / kidx_t; V: vmat, vlut_rows, vnorm->lut_rows2 where present, voutliers / vidx -- and columns
+ * c0 + n_keep .. c0 + S - 1 are zero afterwards, as a cache that never held them.  The keys are stored pre-RoPE and a
+ * column's bytes do not depend on its position, so the result is bit for bit the cache that took only the kept tokens.
+ * keep: HOST memory, n_keep entries, strictly ascending, keep[0] == 0 (the root stays), keep[j] < S; 1 <= n_keep <= S <=
+ * 32, c0 + S <= max_len.  One launch; a layer with kmat == NULL (or vmat == NULL) moves the other side only.  The
+ * reference outlier format only (thr_k > 0 needs the value AND index arrays of every side that is moved: a compact
+ * cache is refused).  Every violation is KVQ_EINVAL before the launch. */
+KVQ_API int kvq_keep_columns(const kvq_layer *layer, int64_t c0, int S, const uint8_t *keep /* HOST */, int n_keep,
+                             void *stream);
 
 /* ---- uncapped ("orig") Dense-and-Sparse variants, 4 bit only ------------------ */
 

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import ops
 from . import rope as rope_mod
-from .cache import QuantK, QuantV, chunk_kv, decode_kv
+from .cache import QuantK, QuantV, chunk_kv, decode_kv, keep_kv
 
 # q_len > 1 on a warm cache (multi-turn prompts, draft verification, chunked fills) takes kvq_chunk_attention
 # (cache.chunk_kv).  KVQ_CHUNK_ATTEND=0 feeds such chunks through the q_len == 1 path token by token instead (A/B runs).
@@ -41,6 +41,20 @@ def chunk_route(klen, q_len, sinks, fast):
     if rest:
         route.append(("chunk", rest) if (fast and rest >= 2) else ("token", rest))
     return route
+
+
+_DEPTHS = {}      # the last tree's (depth index tensor, positions) per device: every layer of a model asks for the same
+
+
+def _depth_index(parent, device):
+    """(int64 tensor of the rows' depths on `device`, max depth + 1) of a draft tree's parent list"""
+    key = (tuple(parent), str(device))
+    hit = _DEPTHS.get("last")
+    if hit is None or hit[0] != key:
+        depth, _ = ops.tree_tables(parent)
+        hit = (key, torch.tensor(depth, device=device), max(depth) + 1)
+        _DEPTHS["last"] = hit
+    return hit[1], hit[2]
 
 
 def rotate_half(x):
@@ -126,6 +140,9 @@ def gqa_groups(num_heads, num_key_value_heads=None):
 
 class KVQuantAttention(nn.Module):
     fuse_sinks = True     # decode: the fp16 sink tokens' matmuls inside the decode launches (False: torch glue as in the reference)
+    # draft tree of the NEXT multi-token attend(): the parent list of its rows (row 0 the root, parent[i] < i), or None.
+    # Set and cleared by the caller (kvquant_amd.llama.draft_tree); see _attend_chunk and keep_path
+    tree = None
 
     def __init__(self, hidden_size=4096, num_heads=32, abits=4, include_sparse=True, first_few_fp16=0,
                  maxseqlen=4096, rope_theta=10000.0, sparsity_threshold=0.99, device=None,
@@ -201,6 +218,16 @@ class KVQuantAttention(nn.Module):
         kc.truncate(n_tokens)
         vc.truncate(n_tokens)
 
+    def keep_path(self, S, keep):
+        """Of the newest S tokens (the rows of a verified draft tree) keep the rows `keep` (ascending, keep[0] == 0: the
+        accepted root-to-leaf path) in both caches, one launch (cache.keep_kv -> kvq_keep_columns); the lengths move back
+        by S - len(keep).  keep = 0 .. n-1 is rollback(S - n).  Refused like rollback, and for compact caches."""
+        kc = self.kcache
+        if kc.klen < self.first_few_fp16:
+            raise ValueError("keep_path while the fp16 sink cache is still filling (len %d < %d)"
+                             % (kc.klen, self.first_few_fp16))
+        keep_kv(kc, self.vcache, S, keep)
+
     # ------------------------------------------------------------------ core (post-projection states)
     def _sink_caches(self):
         """(k_sink, v_sink) of decode_kv / chunk_kv: the fp16 sink caches, or (None, None) without sink tokens"""
@@ -215,6 +242,9 @@ class KVQuantAttention(nn.Module):
         group, one-call decode -- and refuses the configurations for which MHA falls back to the multi-launch tail."""
         bsz, H, q_len, hd = query_states.shape
         assert bsz == 1, "batch 1 only (ML:1801)"
+        if self.tree is not None and not (q_len > 1 and self.kcache.klen > 0):
+            raise ValueError("draft tree of %d rows: a chunk of %d row(s) on a cache of %d tokens is no tree round"
+                             % (len(self.tree), q_len, self.kcache.klen))
         if q_len > 1 and self.kcache.klen > 0:
             return self.attend_multi(query_states, key_states, value_states)
         G = self.num_kv_groups
@@ -320,6 +350,17 @@ class KVQuantAttention(nn.Module):
         one at a time through the q_len == 1 path, the rest through chunk_kv (the chunk's own tokens are attended AS
         STORED, compressed, like token-by-token decoding) -- or one at a time where chunk_fast() is False."""
         q_len = query_states.shape[2]
+        if self.tree is not None:
+            # a tree cannot be fed token by token: every refusal is an error
+            if not self.chunk_fast(query_states):
+                raise ValueError("draft tree: this layer's configuration does not take the chunk kernel (it needs "
+                                 "include_sparse caches in the reference outlier format, fp16 activations, head_dim 128)")
+            if self.kcache.klen < self.first_few_fp16:
+                raise ValueError("draft tree while the fp16 sink cache is still filling (len %d < %d)"
+                                 % (self.kcache.klen, self.first_few_fp16))
+            if q_len != len(self.tree):
+                raise ValueError("draft tree of %d rows, chunk of %d" % (len(self.tree), q_len))
+            return self._attend_chunk(query_states, key_states, value_states).to(query_states.dtype)
         route = chunk_route(self.kcache.klen, q_len, self.first_few_fp16, self.chunk_fast(query_states))
         outs, i = [], 0
         for kind, n in route:
@@ -338,12 +379,19 @@ class KVQuantAttention(nn.Module):
         kvq_rope_q_f16 does for one token), pack + kvq_chunk_attention"""
         bsz, H, q_len, hd = query_states.shape
         start = self.kcache.klen
-        cos, sin = self.rotary_emb(value_states, start, start + q_len)
+        if self.tree is not None:
+            # row i at the position of its depth: the rotary rows of klen .. klen + max depth, indexed by depth
+            idx, n_pos = _depth_index(self.tree, query_states.device)
+            cos, sin = self.rotary_emb(value_states, start, start + n_pos)
+            cos, sin = cos[idx], sin[idx]
+        else:
+            cos, sin = self.rotary_emb(value_states, start, start + q_len)
         query_rope = (query_states * cos) + (rotate_half(query_states) * sin)
         k = key_states[0].half().transpose(1, 2)
         v = value_states[0].half().transpose(1, 2)
         k_sink, v_sink = self._sink_caches()
-        out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v, k_sink=k_sink, v_sink=v_sink)
+        kw = {} if self.tree is None else dict(parent=self.tree)      # (no tree: the call of every release before)
+        out = chunk_kv(self.kcache, self.vcache, query_rope[0], k, v, k_sink=k_sink, v_sink=v_sink, **kw)
         return out.to(query_states.dtype).view(bsz, q_len, self.hidden_size)
 
     def forward(self, hidden_states):

@@ -56,6 +56,19 @@ def _truncate_columns(length, sinks, n_tokens):
     return hi - n, hi
 
 
+def _keep_columns(length, sinks, S, keep):
+    """(c0, n) of keep_columns(S, keep) on a cache of `length` tokens: the S newest compressed columns start at c0, n of
+    them stay.  The error cases of truncate(S), and a keep list that is no ascending path from row 0."""
+    S = int(S)
+    c0, hi = _truncate_columns(length, sinks, S)
+    keep = [int(x) for x in keep]
+    if not 1 <= S <= ops.MAX_TREE:
+        raise ValueError("keep_columns: 1 <= S <= %d columns, got %d" % (ops.MAX_TREE, S))
+    if not keep or keep[0] != 0 or keep[-1] >= S or any(b <= a for a, b in zip(keep, keep[1:])):
+        raise ValueError("keep_columns: keep must start at 0 (the root) and ascend strictly below S = %d, got %r" % (S, keep))
+    return c0, len(keep)
+
+
 def _default_device(device):
     if device is not None:
         return torch.device(device)
@@ -203,6 +216,22 @@ class QuantK(nn.Module):
                 if t is not None:
                     t[:, lo:hi] = 0
         self.klen -= hi - lo
+
+    def keep_columns(self, S, keep):
+        """Of the newest S <= 32 compressed tokens (the nodes of a verified draft tree, packed in row order) keep the
+        len(keep) tokens `keep` names (strictly ascending rows, keep[0] == 0: the accepted root-to-leaf path): they move
+        into the first columns of the chunk, the rest is zero again and klen moves back by S - len(keep) -- one launch
+        (kvq_keep_columns).  The keys are stored pre-RoPE, so the cache is then bit for bit the one that took only the
+        kept tokens; keep = 0 .. n-1 leaves what truncate(S - n) leaves.  The error cases of truncate; compact caches
+        (no value arrays) are refused with ValueError."""
+        if self.use_orig_sparse:
+            raise NotImplementedError("keep_columns: the uncapped (orig) CSR state grows by concatenation")
+        if self.compact:
+            raise ValueError("keep_columns moves the reference outlier format; compact caches are not taken")
+        c0, n = _keep_columns(self.klen, self.first_few_fp16, S, keep)
+        layer, alive = ops.side_layer(kc=self)
+        ops.keep_columns(layer, c0, S, keep, self.device)
+        self.klen -= int(S) - n
 
     def load_lookup_table(self, quantizer, include_sparse=True, sparsity_threshold=0.99, norm=False):
         """ML:437-501.  thresholds -> fp16; offset / range formed in fp16;
@@ -458,6 +487,16 @@ class QuantV(nn.Module):
                 self.outliers[lo:hi] = 0
             self.outlier_indices[lo:hi] = 0
         self.vlen -= hi - lo
+
+    def keep_columns(self, S, keep):
+        """QuantK.keep_columns for the value cache: packed words, codebook rows (both tables) and outlier rows of the kept
+        tokens move to the front of the chunk's columns, the rest is zero again; vlen moves back by S - len(keep)."""
+        if self.compact:
+            raise ValueError("keep_columns moves the reference outlier format; compact caches are not taken")
+        c0, n = _keep_columns(self.vlen, self.first_few_fp16, S, keep)
+        layer, alive = ops.side_layer(vc=self)
+        ops.keep_columns(layer, c0, S, keep, self.device)
+        self.vlen -= int(S) - n
 
     def load_lookup_table(self, quantizer, include_sparse=True, sparsity_threshold=0.99, norm=False):
         """ML:1045-1066: only the sorted global centroids are kept; per-token
@@ -790,7 +829,22 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
 CHUNK_PIECE = 4096      # query rows per kvq_chunk_attention call (bounds its partials workspace)
 
 
-def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
+def keep_kv(kc, vc, S, keep):
+    """QuantK.keep_columns + QuantV.keep_columns of one layer in ONE launch (the layer's struct names both sides): the
+    accepted path of a draft tree stays, klen / vlen move back by S - len(keep).  Nothing changes if it raises."""
+    if getattr(kc, "use_orig_sparse", False):
+        raise NotImplementedError("keep_columns: the uncapped (orig) CSR state grows by concatenation")
+    if not (kc.include_sparse and vc.include_sparse) or kc.compact or vc.compact:
+        raise ValueError("keep_columns moves Dense-and-Sparse caches in the reference outlier format (not compact)")
+    if kc.klen != vc.vlen:
+        raise ValueError("keep_columns: K and V caches are out of step (%d / %d tokens)" % (kc.klen, vc.vlen))
+    c0, n = _keep_columns(kc.klen, kc.first_few_fp16, S, keep)
+    ops.keep_columns(layer_struct(kc, vc), c0, S, keep, kc.device)
+    kc.klen -= int(S) - n
+    vc.vlen -= int(S) - n
+
+
+def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None, parent=None):
     """A chunk of S >= 1 new tokens through a layer's compressed KV path (multi-turn follow-up prompts, draft
     verification, chunked fills): the chunk's K / V are packed into compressed columns c0 .. c0+S-1, c0 = klen - sinks
     (parallel_pack: the fused packs, bit-identical to S decode appends), then ONE kvq_chunk_attention call (MFMA flash
@@ -798,6 +852,10 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
     q: fp16 [Hq, S, 128] RoPE'd at positions klen .. klen+S-1 (any strides with a contiguous last dimension); k, v:
     [Hkv, 128, S] pre-RoPE (as parallel_pack).  k_sink (f16 [Hkv, 128, n_sink], post-RoPE) / v_sink (f16 [Hkv, n_sink,
     128]): the fp16 sink caches, required when the caches count sink tokens.  Hq = G * Hkv, 1 <= G <= 8.
+    parent (a host sequence of S ints, 2 <= S <= 32): the chunk is a draft TREE in topological order -- row 0 the root,
+    parent[i] < i (parent[0] ignored).  The packs are the same (a column's bytes do not depend on its position); the
+    attention is kvq_chunk_attention_tree: query i (RoPE'd by the caller at klen + depth[i]) sees the cache, itself and
+    its ancestors, and column c0 + j rotates at the position of its depth.  keep_kv() then keeps the accepted path.
     Returns f32 [S, Hq, 128].  Dense-and-Sparse caches in the reference outlier format (not compact) only."""
     if not (kc.include_sparse and vc.include_sparse):
         raise ValueError("chunk_kv needs include_sparse caches")
@@ -815,6 +873,17 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None):
     c0 = kc.klen - sinks
     if c0 + S > kc.max_len:
         raise ValueError("chunk_kv: %d + %d tokens exceed the cache (%d columns)" % (c0, S, kc.max_len))
+    if parent is not None:
+        if len(parent) != S:
+            raise ValueError("chunk_kv: %d rows, parent has %d entries" % (S, len(parent)))
+        par = ops.tree_parent_array(parent)            # (ValueError before anything is packed)
+        # (dynamic: the table of the deepest row's position)
+        rope = None if kc.rope.is_default else kc.rope_table(kc.klen + max(ops.tree_tables(parent)[0]) + 1)
+        kc.parallel_pack(k)
+        vc.parallel_pack(v)
+        return ops.chunk_attention_tree(layer_struct(kc, vc), Hq, c0, q, par,
+                                        k_sink=None if sinks == 0 else k_sink.contiguous(),
+                                        v_sink=None if sinks == 0 else v_sink.contiguous(), rope=rope)
     rope = kc.rope_table(kc.klen + S)      # (dynamic: the table of the chunk's last position, for every column)
     kc.parallel_pack(k)
     vc.parallel_pack(v)

@@ -27,6 +27,15 @@
 // head and one split; wave w < G owns the S rows of query head hk * G + w (one 32-row MFMA block, rows >= S clamped
 // duplicates that are never written), waves >= G own no rows but decode with the others.  The tile is then decoded ONCE
 // for the G heads of the group instead of once per query head; partials and merge are unchanged.
+//
+// Tree variant (TR, kvq_chunk_attention_tree: the grouped geometry, 1 <= G <= 8, 2 <= S <= 32 -- verification of a draft
+// TREE): the chunk's rows are the nodes of a tree in topological order (row 0 the root).  Row i sees every column < c0
+// and column c0 + j iff node j is i itself or one of its ancestors (bit j of anc[i]); column c0 + j rotates at the
+// position of its DEPTH, pos_offset + c0 + depth[j], so siblings share a position.  anc / depth ride in the kernel
+// arguments (Tree below).  A chain (parent[i] = i - 1) is the grouped kernel, bit for bit.
+//
+// kvq_keep_columns (end of the file): after a tree round the accepted root-to-leaf path moves into contiguous columns
+// -- a copy of packed words, codebook rows and outlier rows; the keys are stored pre-RoPE, nothing is re-rotated.
 #include "kvq_common.h"
 #include "kvq_host.h"
 
@@ -73,6 +82,12 @@ struct Args {
   float rope_theta, scale_log2e;
 };
 
+// TR: the tree of a chunk of S <= 32 rows, by value in the kernel arguments
+struct Tree {
+  uint32_t anc[kQB];                 // bit j of anc[i]: node j is i or an ancestor of i
+  uint8_t depth[kQB];                // edges from the root (row 0)
+};
+
 __device__ __forceinline__ uint32_t pack_f16(float a, float b) {
   uint32_t r;
   asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -90,10 +105,14 @@ __device__ __forceinline__ uint32_t pack_f16(float a, float b) {
   __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];        \
   __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow]; \
   __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
-template <int BITS, bool RT, bool GR = false>
+// TR (with GR only): tree mask and per-node positions from the LDS copies tanc [32] / tdepth [32] of a Tree, which the
+// kernel wrote before the call (chunk_attn_tree_kernel below; the barriers in front of the first use order them)
+template <int BITS, bool RT, bool GR = false, bool TR = false>
 __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, float *theta, float *vrow, float *kst,
                                                 float *vst, unsigned char *k16, unsigned char *vt16, const float *rt_freq,
-                                                float rt_af) {
+                                                float rt_af, const uint32_t *tanc = nullptr,
+                                                const int *tdepth = nullptr) {
+  static_assert(!TR || GR, "the tree variant runs in the grouped geometry");
   constexpr int N = 1 << BITS;
   constexpr int WPH = kD / 32 * BITS;
 
@@ -144,7 +163,8 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
   float m_run = -INFINITY, l_run = 0.f;
 
   // ---- S^T, mask, online softmax, O^T of one staged tile.  sink: key j of the tile is sink token j (no causal mask);
-  // else key j is compressed column t0 + j, visible to row q iff t0 + j <= c0 + q (and < Lc)
+  // else key j is compressed column t0 + j, visible to row q iff t0 + j <= c0 + q (and < Lc); TR: iff t0 + j < c0 or
+  // node t0 + j - c0 is in the row's ancestor set (which has no bit at or above S)
   auto attend_tile = [&](bool sink, int64_t t0) __attribute__((always_inline)) {
     const bool active = has_rows && q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1);
     if (!active) return;
@@ -161,7 +181,18 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
         sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sacc[kb], 0, 0, 0);
       }
     }
-    const bool diag = sink ? a.n_sink < kKV : (t0 + kKV - 1 > a.c0 + q0 || t0 + kKV > Lc);
+    const bool diag = sink ? a.n_sink < kKV : TR ? t0 + kKV > a.c0 : (t0 + kKV - 1 > a.c0 + q0 || t0 + kKV > Lc);
+    // TR: bit j of vism[kb] = key kb * 32 + 4 * hi + j of the tile is visible to this lane's row (rows >= S: no node)
+    uint32_t vism[2] = {0u, 0u};
+    if constexpr (TR) {
+      if (diag && !sink) {
+        const int rel = (int)(t0 - a.c0);              // node of the tile's first key; > -64 (diag), <= S - 1
+        const uint64_t an = tanc[ql];
+        const uint64_t m = rel >= 0 ? an >> rel : (an << -rel) | ((uint64_t(1) << -rel) - 1);
+        vism[0] = (uint32_t)m >> (4 * hi);
+        vism[1] = (uint32_t)(m >> 32) >> (4 * hi);
+      }
+    }
     float mx = -INFINITY;
 #pragma unroll
     for (int kb = 0; kb < 2; kb++)
@@ -170,7 +201,12 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
         float s = sacc[kb][r];
         if (diag) {
           const int j = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          const bool vis = sink ? j < a.n_sink : (t0 + j <= a.c0 + qrow && t0 + j < Lc);
+          bool vis;
+          if constexpr (TR) {
+            vis = sink ? j < a.n_sink : (vism[kb] >> ((r & 3) + 8 * (r >> 2))) & 1u;
+          } else {
+            vis = sink ? j < a.n_sink : (t0 + j <= a.c0 + qrow && t0 + j < Lc);
+          }
           if (!vis) s = -INFINITY;
           sacc[kb][r] = s;
         }
@@ -289,10 +325,15 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
       }
     }
     __syncthreads();
-    // P3: K: RoPE of pairs (j, j + 64), j = 16g .. 16g+15, at position pos_offset + column -> fp16 K tile;
-    //     V: channels 32g .. 32g+31 -> fp16 V^T tile
+    // P3: K: RoPE of pairs (j, j + 64), j = 16g .. 16g+15, at position pos_offset + column (TR: a column of the chunk
+    //     at pos_offset + c0 + its node's depth) -> fp16 K tile;  V: channels 32g .. 32g+31 -> fp16 V^T tile
     if (is_k) {
-      const float posf = (float)((int)colc + a.pos_offset);
+      int pos = (int)colc;
+      if constexpr (TR) {
+        const int node = (int)(colc - a.c0);           // <= S - 1 (colc < Lc)
+        if (node >= 0) pos = (int)a.c0 + tdepth[node];
+      }
+      const float posf = (float)(pos + a.pos_offset);
       const float *kr = kst + skey * kSR;
       float lo[16], hv[16];
 #pragma unroll
@@ -370,7 +411,30 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_grouped_kernel_rt(Args
   KVQ_CHUNK_LDS
   chunk_attn_body<BITS, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af);
 }
+// the tree kernels' LDS copies of their Tree argument
+#define KVQ_CHUNK_TREE_LDS                   \
+  __shared__ uint32_t tanc[kQB];             \
+  __shared__ int tdepth[kQB];                \
+  if (threadIdx.x < kQB) {                   \
+    tanc[threadIdx.x] = tr.anc[threadIdx.x]; \
+    tdepth[threadIdx.x] = tr.depth[threadIdx.x]; \
+  }
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_tree_kernel(Args a, Tree tr) {
+  KVQ_CHUNK_LDS
+  KVQ_CHUNK_TREE_LDS
+  chunk_attn_body<BITS, false, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, nullptr, 1.f, tanc, tdepth);
+}
+
+template <int BITS>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_tree_kernel_rt(Args a, Tree tr, const float *rt_freq,
+                                                                         float rt_af) {
+  KVQ_CHUNK_LDS
+  KVQ_CHUNK_TREE_LDS
+  chunk_attn_body<BITS, true, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af, tanc, tdepth);
+}
 #undef KVQ_CHUNK_LDS
+#undef KVQ_CHUNK_TREE_LDS
 
 // out[s][h][:] = sum_split w * O_split / sum_split w * l_split, w = 2^((m_split - M) * c), splits in index order
 __global__ __launch_bounds__(kD) void chunk_attn_merge_kernel(const float *__restrict__ part_o,
@@ -401,11 +465,13 @@ struct Plan {
 static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // grouped: the plan of the grouped kernel (G >= 2, S <= 32): Hkv workgroup rows in place of Hq x nqb
-static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = false) {
+// tree (with grouped): the tree variant also takes G = 1, and a tree has at least one draft node (S >= 2)
+static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = false, bool tree = false) {
   if (Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 8 || (int64_t)Hkv * kD > 8192 || S <= 0 || S > kMaxS || c0 < 0 ||
       c0 + S >= (int64_t(1) << 31))
     return false;
-  if (grouped && (Hq / Hkv < 2 || S > kQB)) return false;
+  if (grouped && ((Hq / Hkv < 2 && !tree) || S > kQB)) return false;
+  if (tree && S < 2) return false;
   p.nqb = (S + kQW - 1) / kQW;
   const int64_t tiles = (c0 + S + kKV - 1) / kKV;
   const int64_t base = grouped ? (int64_t)Hkv : (int64_t)Hq * p.nqb;
@@ -428,16 +494,37 @@ static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = fal
 
 using namespace kvq;
 
+// depth and ancestor sets of a tree of S rows from its parent array (HOST memory; parent[0] is ignored): false unless
+// 2 <= S <= 32 and parent[i] < i for every draft node
+static bool tree_of(const uint8_t *parent, int S, chunk::Tree &t) {
+  if (!parent || S < 2 || S > chunk::kQB) return false;
+  for (int i = 0; i < chunk::kQB; i++) {
+    t.anc[i] = 0;
+    t.depth[i] = 0;
+  }
+  t.anc[0] = 1u;
+  for (int i = 1; i < S; i++) {
+    const int p = parent[i];
+    if (p >= i) return false;
+    t.depth[i] = (uint8_t)(t.depth[p] + 1);
+    t.anc[i] = t.anc[p] | (1u << i);
+  }
+  return true;
+}
+
 // grouped: the grouped kernel (one workgroup per KV head and split), which plan() takes for G >= 2 and S <= 32 only
+// parent (with grouped; HOST array of S entries): the tree variant, G >= 1 and 2 <= S <= 32
 static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
                                   int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink,
                                   float *out, void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream,
-                                  bool grouped) {
+                                  bool grouped, const uint8_t *parent = nullptr) {
   if (!ly || !q || !out || !rope_ok(rope)) return KVQ_EINVAL;
+  chunk::Tree tree;
+  if (parent && !(grouped && tree_of(parent, S, tree))) return KVQ_EINVAL;
   const int bits = ly->bits;
   if ((bits != 2 && bits != 3 && bits != 4) || ly->hd != chunk::kD || ly->thr_k <= 0) return KVQ_EINVAL;
   chunk::Plan p;
-  if (!chunk::plan(Hq, ly->H, S, c0, p, grouped)) return KVQ_EINVAL;
+  if (!chunk::plan(Hq, ly->H, S, c0, p, grouped, parent != nullptr)) return KVQ_EINVAL;
   if (ly->max_len <= 0 || ly->max_len >= (int64_t(1) << 31) || c0 + S > ly->max_len || ly->pos_offset < 0 ||
       c0 + S + ly->pos_offset >= (int64_t(1) << 31))
     return KVQ_EINVAL;
@@ -484,7 +571,17 @@ static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0
   a.scale_log2e = (1.0f / sqrtf((float)chunk::kD)) * 1.4426950408889634f;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((int64_t)(grouped ? ly->H : Hq * p.nqb) * p.nsplit)), block(chunk::kThreads);
-  if (grouped && rope) {
+  if (parent && rope) {
+    const float *f = rope->inv_freq;
+    const float af = rope->attention_factor;
+    if (bits == 4) chunk::chunk_attn_tree_kernel_rt<4><<<grid, block, 0, st>>>(a, tree, f, af);
+    else if (bits == 3) chunk::chunk_attn_tree_kernel_rt<3><<<grid, block, 0, st>>>(a, tree, f, af);
+    else chunk::chunk_attn_tree_kernel_rt<2><<<grid, block, 0, st>>>(a, tree, f, af);
+  } else if (parent) {
+    if (bits == 4) chunk::chunk_attn_tree_kernel<4><<<grid, block, 0, st>>>(a, tree);
+    else if (bits == 3) chunk::chunk_attn_tree_kernel<3><<<grid, block, 0, st>>>(a, tree);
+    else chunk::chunk_attn_tree_kernel<2><<<grid, block, 0, st>>>(a, tree);
+  } else if (grouped && rope) {
     const float *f = rope->inv_freq;
     const float af = rope->attention_factor;
     if (bits == 4) chunk::chunk_attn_grouped_kernel_rt<4><<<grid, block, 0, st>>>(a, f, af);
@@ -553,6 +650,140 @@ int kvq_chunk_attention_grouped_rope(const kvq_layer *ly, int Hq, int S, int64_t
                                      void *stream) {
   return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
                                 workspace_bytes, rope, stream, true);
+}
+
+size_t kvq_chunk_attention_tree_workspace_bytes(int Hq, int Hkv, int S, int64_t c0) {
+  chunk::Plan p;
+  if (!chunk::plan(Hq, Hkv, S, c0, p, true, true)) return 0;
+  return p.o_bytes + p.ml_bytes;
+}
+
+int kvq_chunk_attention_tree(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                             int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                             void *workspace, size_t workspace_bytes, const uint8_t *parent, void *stream) {
+  if (!parent) return KVQ_EINVAL;
+  return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, nullptr, stream, true, parent);
+}
+
+int kvq_chunk_attention_tree_rope(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
+                                  int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink,
+                                  float *out, void *workspace, size_t workspace_bytes, const uint8_t *parent,
+                                  const kvq_rope *rope, void *stream) {
+  if (!parent) return KVQ_EINVAL;
+  return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, rope, stream, true, parent);
+}
+
+}  // extern "C"
+
+// ---- kvq_keep_columns: the accepted path of a tree round moves into contiguous columns ---------------------------------
+// Every array in which a column owns storage holds 4-byte elements, either as rows along the columns (packed words, the
+// K outlier mirror: element (r, c) at r * max_len + c) or as token-major rows (codebook rows, outlier rows: element
+// (c, e) at c * width + e).  A thread owns ONE storage position (a word row r, or an entry slot e) across the chunk's S
+// columns: it loads its n_keep sources c0 + keep[j] into registers, then stores them to c0 + j and zeros to the columns
+// behind -- keep[j] >= j makes a destination another element's source, but only ever within one thread's position, and
+// every load of a thread precedes its first store.  One launch for all arrays of the layer (a few hundred threads).
+namespace kvq {
+namespace keep {
+
+constexpr int kMaxS = 32;
+constexpr int kMaxJobs = 10;
+constexpr int kThreads = 256;
+
+struct Jobs {
+  uint32_t *base[kMaxJobs];
+  int64_t pos_stride[kMaxJobs];      // elements between two storage positions
+  int64_t col_stride[kMaxJobs];      // elements between two columns
+  int first[kMaxJobs + 1];           // job i owns threads [first[i], first[i + 1])
+  int n_jobs, S, n_keep;
+  int64_t c0;
+  uint8_t keep[kMaxS];
+};
+
+__global__ __launch_bounds__(kThreads) void keep_columns_kernel(Jobs jb) {
+  const int gid = (int)(blockIdx.x * kThreads + threadIdx.x);
+  uint32_t *p = nullptr;
+  int64_t cs = 0;
+#pragma unroll
+  for (int i = 0; i < kMaxJobs; i++)
+    if (i < jb.n_jobs && gid >= jb.first[i] && gid < jb.first[i + 1]) {
+      p = jb.base[i] + (int64_t)(gid - jb.first[i]) * jb.pos_stride[i] + jb.c0 * jb.col_stride[i];
+      cs = jb.col_stride[i];
+    }
+  if (!p) return;
+  uint32_t v[kMaxS];
+#pragma unroll
+  for (int j = 0; j < kMaxS; j++) v[j] = j < jb.n_keep ? p[(int64_t)jb.keep[j] * cs] : 0u;
+#pragma unroll
+  for (int j = 0; j < kMaxS; j++)
+    if (j < jb.S) p[(int64_t)j * cs] = v[j];
+}
+
+}  // namespace keep
+}  // namespace kvq
+
+extern "C" {
+
+int kvq_keep_columns(const kvq_layer *ly, int64_t c0, int S, const uint8_t *keep_idx, int n_keep, void *stream) {
+  if (!ly || !keep_idx) return KVQ_EINVAL;
+  const int bits = ly->bits;
+  if ((bits != 2 && bits != 3 && bits != 4) || ly->H <= 0 || ly->hd <= 0 || ly->hd % 32 || ly->thr_k < 0)
+    return KVQ_EINVAL;
+  if (S < 1 || S > keep::kMaxS || n_keep < 1 || n_keep > S || c0 < 0 || ly->max_len <= 0 || c0 + S > ly->max_len)
+    return KVQ_EINVAL;
+  if (keep_idx[0] != 0) return KVQ_EINVAL;
+  for (int j = 1; j < n_keep; j++)
+    if (keep_idx[j] <= keep_idx[j - 1] || keep_idx[j] >= S) return KVQ_EINVAL;
+  if (!ly->kmat && !ly->vmat) return KVQ_EINVAL;
+  const int64_t ml = ly->max_len;
+  const int64_t words = (int64_t)ly->H * (ly->hd / 32) * bits;
+  const int n_out = 2 * ly->thr_k, N = 1 << bits;
+  if (words > (1 << 20) || n_out > (1 << 20)) return KVQ_EINVAL;
+  keep::Jobs jb;
+  int n = 0, total = 0;
+  auto add = [&](void *base, int positions, int64_t pos_stride, int64_t col_stride) {
+    jb.base[n] = reinterpret_cast<uint32_t *>(base);
+    jb.pos_stride[n] = pos_stride;
+    jb.col_stride[n] = col_stride;
+    jb.first[n] = total;
+    total += positions;
+    n++;
+  };
+  if (ly->kmat) {
+    // the reference outlier format: rows and mirror, values and indices (a compact cache keeps no value arrays)
+    if (n_out > 0 && (!ly->koutliers || !ly->kidx || !ly->koutliers_t || !ly->kidx_t)) return KVQ_EINVAL;
+    add(ly->kmat, (int)words, ml, 1);
+    if (n_out > 0) {
+      add(ly->koutliers_t, n_out, ml, 1);
+      add(ly->kidx_t, n_out, ml, 1);
+      add(ly->koutliers, n_out, 1, n_out);
+      add(ly->kidx, n_out, 1, n_out);
+    }
+  }
+  if (ly->vmat) {
+    if (!ly->vlut_rows || (n_out > 0 && (!ly->voutliers || !ly->vidx))) return KVQ_EINVAL;
+    add(ly->vmat, (int)words, ml, 1);
+    add(ly->vlut_rows, N, 1, N);
+    if (ly->vnorm && ly->vnorm->lut_rows2) add(ly->vnorm->lut_rows2, N, 1, N);
+    if (n_out > 0) {
+      add(ly->voutliers, n_out, 1, n_out);
+      add(ly->vidx, n_out, 1, n_out);
+    }
+  }
+  for (int i = n; i < keep::kMaxJobs; i++) {
+    jb.base[i] = nullptr;
+    jb.pos_stride[i] = jb.col_stride[i] = 0;
+  }
+  for (int i = n; i <= keep::kMaxJobs; i++) jb.first[i] = total;
+  jb.n_jobs = n;
+  jb.S = S;
+  jb.n_keep = n_keep;
+  jb.c0 = c0;
+  for (int j = 0; j < keep::kMaxS; j++) jb.keep[j] = j < n_keep ? keep_idx[j] : 0;
+  const unsigned blocks = (unsigned)((total + keep::kThreads - 1) / keep::kThreads);
+  keep::keep_columns_kernel<<<blocks, keep::kThreads, 0, (hipStream_t)stream>>>(jb);
+  return check_launch();
 }
 
 }  // extern "C"

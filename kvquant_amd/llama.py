@@ -37,6 +37,7 @@ for machines without network, `synthetic` (seeded random token ids) or a path to
 """
 import os
 import pickle
+import contextlib
 import time
 import types
 
@@ -46,7 +47,7 @@ import torch.nn as nn
 from . import sharding
 from .attention import KVQuantAttention, gqa_groups
 from .rope import RopeSpec
-from .spec import MAX_DRAFT, accept_draft, ngram_draft
+from .spec import MAX_DRAFT, accept_draft, accept_tree, cut_tree, ngram_draft, ngram_tree_draft
 
 KNOBS = dict(dynamicrope=True, use_orig_sparse=False, first_few_fp16=0, maxseqlen=-1, abits=4, include_sparse=False)
 
@@ -153,6 +154,50 @@ def rollback(model, n_tokens):
                              % (n_tokens, core.kcache.klen, core.vcache.vlen, core.first_few_fp16))
     for core in cores:
         core.rollback(n_tokens)
+
+
+def _cores(model):
+    base = model.model if hasattr(model, "model") else model
+    return [layer.self_attn.kvq for layer in base.layers]
+
+
+@contextlib.contextmanager
+def draft_tree(model, parent):
+    """While the context is open, the model's next multi-token forward is a draft TREE: its rows are the nodes in
+    topological order, row 0 the root (the last real token), parent[i] < i the parent row of node i (parent[0] is
+    ignored).  Every layer rotates query row i at klen + depth[i] and attends under the tree mask
+    (KVQuantAttention.tree -> cache.chunk_kv(parent=...)); a layer that cannot refuses with ValueError.  Cleared on
+    exit; keep_path() afterwards keeps the accepted path."""
+    parent = [0] + [int(p) for p in list(parent)[1:]]
+    cores = _cores(model)
+    for core in cores:
+        core.tree = parent
+    try:
+        yield parent
+    finally:
+        for core in cores:
+            core.tree = None
+
+
+def keep_path(model, S, keep):
+    """of the newest S tokens of every layer's caches (the rows of a verified draft tree) keep the rows `keep`
+    (ascending, keep[0] == 0: the accepted root-to-leaf path; KVQuantAttention.keep_path).  The layers are checked first,
+    so that a refusal leaves all of them as they were."""
+    cores = _cores(model)
+    S, keep = int(S), [int(x) for x in keep]
+    if not 1 <= S <= 32 or not keep or keep[0] != 0 or keep[-1] >= S or any(b <= a for a, b in zip(keep, keep[1:])):
+        raise ValueError("keep_path(%d, %r): 1 <= S <= 32 and keep ascends strictly from 0 below S" % (S, keep))
+    for core in cores:
+        kc, vc = core.kcache, core.vcache
+        if getattr(kc, "use_orig_sparse", False):
+            raise NotImplementedError("keep_path: the uncapped (orig) CSR state grows by concatenation")
+        if not (kc.include_sparse and vc.include_sparse) or kc.compact or vc.compact:
+            raise ValueError("keep_path moves Dense-and-Sparse caches in the reference outlier format (not compact)")
+        if kc.klen != vc.vlen or kc.klen < core.first_few_fp16 or S > kc.klen - core.first_few_fp16:
+            raise ValueError("keep_path(%d): a layer holds %d / %d tokens, %d of them fp16 sink tokens"
+                             % (S, kc.klen, vc.vlen, core.first_few_fp16))
+    for core in cores:
+        core.keep_path(S, keep)
 
 
 def load_quantizers(model, quantizers, include_sparse=True, sparsity_threshold=0.99, norm=False):
@@ -356,7 +401,7 @@ def _warp_logits(logits, temperature, top_k, top_p):
 @torch.no_grad()
 def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_id=None, pad_token_id=None,
              do_sample=False, temperature=1.0, top_k=50, top_p=1.0, min_length=0, generator=None, draft_len=0,
-             drafter=None, stats=None):
+             drafter=None, stats=None, draft_branches=1):
     """Decoding with the compressed cache: the reference's `model.generate(..., kvquant=True)`
     (generation/utils.py:2325-2416) -- the prompt goes through the model once (parallel pack of its K / V), then every
     step feeds ONLY the newest token (`input_ids = next_tokens[:, None]`, :2378-2380), the returned sequence is the
@@ -375,7 +420,14 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
     equals the model's own arg-max is kept, the next token is the arg-max behind it, and the rejected tail leaves the
     caches again (rollback).  The caches end as plain generate() leaves them; the tokens are the greedy ones up to
     near-ties (a chunk's rows and a single token's take different split plans).  stats (a dict) receives `forwards`
-    (model calls, the prompt's included), `rounds` (those after the prompt), `drafted` and `accepted` (tokens)."""
+    (model calls, the prompt's included), `rounds` (those after the prompt), `drafted` and `accepted` (tokens).
+    draft_branches = b >= 2 (with draft_len = k): draft TREES.  Each round `drafter(seq, k)` returns (tokens, parent) of
+    up to k draft nodes in topological order (default ngram_tree_draft with `branches=b`: the continuations of the b most
+    recent occurrences of the suffix n-gram, merged into a trie), `[last token] + tokens` goes through the model as one
+    forward under the tree mask (draft_tree), accept_tree() walks the arg-max path and keep_path() keeps exactly that
+    path in the caches -- a plain copy: the keys are cached pre-RoPE.  `drafted` counts nodes, `accepted` the path's
+    length.  Refused with ValueError: do_sample, and layers the chunk kernel does not take (compact, no include_sparse,
+    orig, non-fp16).  b = 1 (default) is the chain loop above, call for call."""
     if input_ids.shape[0] != 1:
         raise ValueError("the compressed-cache path is batch 1 (ML:1408)")
     if draft_len:
@@ -383,6 +435,16 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
             raise ValueError("speculative decoding (draft_len > 0) is greedy: do_sample=True is not taken")
         if not 1 <= int(draft_len) <= MAX_DRAFT:
             raise ValueError("draft_len must be 0 (off) or 1 .. %d" % MAX_DRAFT)
+    if int(draft_branches) < 1 or (int(draft_branches) > 1 and not draft_len):
+        raise ValueError("draft_branches must be >= 1, and > 1 only with draft_len > 0")
+    if int(draft_branches) > 1:
+        for core in _cores(model):
+            kc, vc = core.kcache, core.vcache
+            dtype = next(model.parameters()).dtype
+            if not (kc.include_sparse and vc.include_sparse) or kc.compact or vc.compact \
+                    or getattr(kc, "use_orig_sparse", False) or dtype != torch.float16 or core.head_dim != 128:
+                raise ValueError("draft trees (draft_branches > 1) need layers the chunk kernel takes: include_sparse "
+                                 "caches in the reference outlier format (not compact, not orig), fp16, head_dim 128")
     dev = model.gpus[0] if hasattr(model, "gpus") else next(model.parameters()).device
     input_ids = input_ids.to(dev)
     n_prompt = input_ids.shape[1]
@@ -392,6 +454,10 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
         eos_token_id = [eos_token_id]
     if eos_token_id is not None and pad_token_id is None:
         raise ValueError("If `eos_token_id` is defined, make sure that `pad_token_id` is defined.")
+    if draft_len and int(draft_branches) > 1:
+        b = int(draft_branches)
+        return _generate_tree(model, input_ids, max_length, eos_token_id, min_length, int(draft_len),
+                              drafter or (lambda seq, k: ngram_tree_draft(seq, k, branches=b)), stats)
     if draft_len:
         return _generate_speculative(model, input_ids, max_length, eos_token_id, min_length, int(draft_len),
                                      drafter or ngram_draft, stats)
@@ -463,6 +529,57 @@ def _generate_speculative(model, input_ids, max_length, eos_token_id, min_length
     return seq
 
 
+def _generate_tree(model, input_ids, max_length, eos_token_id, min_length, draft_len, drafter, stats):
+    """the draft_branches > 1 loop of generate(): the invariant of _generate_speculative -- the caches hold every token of
+    `seq` but the last; `feed` is that last token (first round: the prompt) followed by the draft nodes (tokens, parent)"""
+    core = _cores(model)[0]
+    seq, feed, tokens, parent = input_ids, input_ids, [], []
+    st = dict(rounds=0, drafted=0, accepted=0, forwards=0)
+    while True:
+        m = len(tokens)
+        if m:
+            with draft_tree(model, [0] + parent) as par:
+                logits = model(feed, use_cache=False).logits[0].float()
+            depth = [0] * (m + 1)
+            for i in range(1, m + 1):
+                depth[i] = depth[par[i]] + 1
+        else:
+            logits = model(feed, use_cache=False).logits[0, feed.shape[1] - 1:, :].float()
+            depth = [0]
+        st["forwards"] += 1
+        st["rounds"] += seq is not input_ids
+        st["drafted"] += m
+        if eos_token_id is not None:
+            for i in range(m + 1):
+                if seq.shape[1] + depth[i] < min_length:        # MinLengthLogitsProcessor at row i's length
+                    logits[i, eos_token_id] = float("-inf")
+        keep, nxt = accept_tree(tokens, parent, logits.argmax(dim=-1).tolist())
+        new = [tokens[i - 1] for i in keep[1:]] + [nxt]
+        st["accepted"] += len(keep) - 1
+        done = False
+        if eos_token_id is not None:
+            for i, t in enumerate(new):
+                if t in eos_token_id:                           # the first EOS ends it; nothing behind it is kept
+                    new, keep, done = new[:i + 1], keep[:i + 1], True
+                    break
+        if len(keep) < m + 1:
+            keep_path(model, m + 1, keep)
+        seq = torch.cat((seq, torch.tensor([new], dtype=seq.dtype, device=seq.device)), dim=-1)
+        if done or seq.shape[1] >= max_length:
+            break
+        # the next tree: its deepest path can never take the sequence past max_length, its nodes never overflow the cache
+        klen, sinks = core.kcache.klen, core.first_few_fp16
+        max_depth = max_length - seq.shape[1] - 1
+        k = min(draft_len, core.kcache.max_len - (klen - sinks) - 1)
+        tokens, parent = [], []
+        if k > 0 and max_depth > 0 and klen >= sinks:
+            tokens, parent = cut_tree(*drafter(seq[0], k), max_nodes=k, max_depth=max_depth)
+        feed = torch.tensor([new[-1:] + tokens], dtype=seq.dtype, device=seq.device)
+    if stats is not None:
+        stats.update(st)
+    return seq
+
+
 def inference_main(argv=None):
     """lwm/llama_inference.py:39-138 (the same arguments): load a long-context Llama with the compressed cache sized by
     --maxseqlen, read the quantizer pickle, sample a continuation of --text and print it with the wall time.
@@ -487,6 +604,9 @@ def inference_main(argv=None):
     ap.add_argument("--draft-len", type=int, default=0,
                     help="(extra) speculative decoding: verify up to this many prompt-lookup draft tokens per forward "
                          "(1 .. 31, with --greedy; 0: off)")
+    ap.add_argument("--draft-branches", type=int, default=1,
+                    help="(extra) with --draft-len: verify a TREE of the continuations of up to this many earlier "
+                         "occurrences of the suffix n-gram per forward (1: a chain)")
     ap.add_argument("--ngram", type=int, default=3, help="(extra) longest n-gram the prompt-lookup drafter matches")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -525,7 +645,11 @@ def inference_main(argv=None):
         with torch.no_grad():
             ids = generate(model, input_ids, max_length=args.max_length, min_length=args.min_length, eos_token_id=eos,
                            pad_token_id=pad, do_sample=not args.greedy, generator=gen, draft_len=args.draft_len,
-                           drafter=lambda seq, k: ngram_draft(seq, k, max_ngram=args.ngram))
+                           draft_branches=args.draft_branches,
+                           drafter=(lambda seq, k: ngram_draft(seq, k, max_ngram=args.ngram))
+                           if args.draft_branches <= 1 else
+                           (lambda seq, k: ngram_tree_draft(seq, k, max_ngram=args.ngram,
+                                                            branches=args.draft_branches)))
         torch.cuda.synchronize()
         t2 = time.time()
     else:

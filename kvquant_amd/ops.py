@@ -824,6 +824,7 @@ def decode_step_gqa(layer, Hq, col, q, k, v, out, sink_scores=None, v_sink=None,
 
 
 # ---- a chunk of S new tokens over the compressed cache (MFMA flash kernel, kvq_chunk_attn.hip) ---------------------
+# (draft trees -- chunk_attention_tree, keep_columns -- at the end of the file)
 # Short chunks under grouped-query attention (G >= 2, S <= 32: draft verification) take the grouped kernel
 # (kvq_chunk_attention_grouped: a K / V tile is decoded once per KV head instead of once per query head).
 # KVQ_CHUNK_GROUPED=0 keeps the per-head kernel for every shape (A/B runs).
@@ -867,3 +868,128 @@ def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=N
             None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
             base, usable, _rope(rope, out.device), _stream()), name + "_rope")
     return out
+
+
+# ---- draft trees: tree mask + per-node positions on the grouped kernel, and the accepted path -------------------------
+MAX_TREE = 32       # rows of a tree chunk (the 32-row block of the grouped kernel), root included
+
+
+def tree_tables(parent):
+    """(depth, anc) of a tree in topological order, as the library derives them from `parent` (parent[0] is ignored,
+    parent[i] < i): depth[0] = 0, depth[i] = depth[parent[i]] + 1; anc[i] = the bit set of i and its ancestors.
+    ValueError for a parent array that is no such tree or has more than MAX_TREE rows."""
+    parent = [int(p) for p in parent]
+    S = len(parent)
+    if not 1 <= S <= MAX_TREE:
+        raise ValueError("a tree chunk has 1 .. %d rows (root included), got %d" % (MAX_TREE, S))
+    depth, anc = [0] * S, [1] + [0] * (S - 1)
+    for i in range(1, S):
+        p = parent[i]
+        if not 0 <= p < i:
+            raise ValueError("parent[%d] = %d: nodes come in topological order (0 <= parent[i] < i)" % (i, p))
+        depth[i] = depth[p] + 1
+        anc[i] = anc[p] | (1 << i)
+    return depth, anc
+
+
+def _host_bytes(values, name, S):
+    values = [int(x) for x in values]
+    if len(values) != S or any(not 0 <= x <= 255 for x in values):
+        raise ValueError("%s: expected %d entries in 0 .. 255" % (name, S))
+    return (ctypes.c_uint8 * S)(*values)
+
+
+def tree_parent_array(parent):
+    """the HOST array kvq_chunk_attention_tree takes, from a sequence of S ints (parent[0] is ignored): one pass that
+    checks 2 <= S <= MAX_TREE and 0 <= parent[i] < i.  ValueError otherwise."""
+    S = len(parent)
+    if not 2 <= S <= MAX_TREE:
+        raise ValueError("a tree chunk has 2 .. %d rows (root + draft nodes), got %d" % (MAX_TREE, S))
+    arr = (ctypes.c_uint8 * S)()
+    for i in range(1, S):
+        p = int(parent[i])
+        if not 0 <= p < i:
+            raise ValueError("parent[%d] = %d: nodes come in topological order (0 <= parent[i] < i)" % (i, p))
+        arr[i] = p
+    return arr
+
+
+def chunk_attention_tree(layer, Hq, c0, q, parent, out=None, k_sink=None, v_sink=None, rope=None):
+    """kvq_chunk_attention_tree: chunk_attention for a draft TREE.  q fp16 [Hq, S, 128], 2 <= S <= 32 rows in
+    topological order (row 0 the root, parent[i] < i the parent row of node i; parent: a host sequence of S ints,
+    parent[0] ignored).  Query i (RoPE'd by the caller at position pos_offset + c0 + depth[i]) attends to the sink
+    tokens, the compressed columns < c0 and the columns c0 + j of itself and its ancestors; column c0 + j is rotated at
+    pos_offset + c0 + depth[j].  The chunk must already be packed into columns c0 .. c0+S-1 in row order.  Every
+    1 <= G <= 8 runs the grouped geometry.  parent may be the array tree_parent_array() made of it (checked there).
+    Returns out f32 [S, Hq, 128]."""
+    if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float16 and q.dim() == 3 and q.stride(2) == 1):
+        raise ValueError("q: expected an fp16 GPU tensor [Hq, S, 128] with a contiguous last dimension")
+    if q.shape[0] != Hq or q.shape[2] != 128:
+        raise ValueError("q: expected [%d, S, 128], got %s" % (Hq, tuple(q.shape)))
+    if (k_sink is None) != (v_sink is None):
+        raise ValueError("k_sink and v_sink come together")
+    S = int(q.shape[1])
+    if len(parent) != S:
+        raise ValueError("chunk_attention_tree: %d rows, parent has %d entries" % (S, len(parent)))
+    par = parent if isinstance(parent, ctypes.Array) else tree_parent_array(parent)
+    n_sink = 0 if k_sink is None else int(k_sink.shape[2])
+    if out is None:
+        out = torch.empty((S, Hq, 128), dtype=torch.float32, device=q.device)
+    with _Dev(out):
+        nbytes = _L().kvq_chunk_attention_tree_workspace_bytes(int(Hq), layer.H, S, int(c0))
+        if nbytes == 0:
+            raise ValueError("chunk_attention_tree: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
+        base, usable, ws = _aligned_workspace(out.device, nbytes, "chunk")
+        _lib.check(_L().kvq_chunk_attention_tree_rope(
+            ctypes.byref(layer), int(Hq), S, int(c0), q.data_ptr(), q.stride(0), q.stride(1),
+            None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
+            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
+            base, usable, par, _rope(rope, out.device), _stream()), "kvq_chunk_attention_tree_rope")
+    return out
+
+
+def side_layer(kc=None, vc=None):
+    """struct kvq_layer that names the column-owning arrays of ONE side (a QuantK or a QuantV) for keep_columns; the
+    other side's pointers are NULL.  Reference outlier format (a compact cache keeps no value arrays: refused by the
+    library).  Returns (struct, keep-alive tuple)."""
+    c = kc if kc is not None else vc
+    mat = kc.kcache if kc is not None else vc.vcache
+    H, hd, max_len = _cache_dims(mat, c.bits)
+    sparse = bool(c.include_sparse)
+    ly = _lib.Layer()
+    ly.bits, ly.H, ly.hd, ly.thr_k, ly.max_len = c.bits, H, hd, (c.num_outliers // 2 if sparse else 0), max_len
+    vstruct = None
+    if kc is not None:
+        ly.kmat = _i(kc.kcache, "kcache")
+        if sparse:
+            ly.koutliers, ly.kidx = _fo(kc.outliers, "outliers"), _io(kc.outlier_indices, "outlier_indices")
+            ly.koutliers_t = _fo(kc.outliers_t, "outliers_t")
+            ly.kidx_t = _io(kc.outlier_indices_t, "outlier_indices_t")
+    else:
+        ly.vmat = _i(vc.vcache, "vcache")
+        ly.vlut_rows = _f(vc.lookup_table, "lookup_table")
+        if sparse:
+            ly.voutliers, ly.vidx = _fo(vc.outliers, "outliers"), _io(vc.outlier_indices, "outlier_indices")
+        if vc.lookup_table2 is not None:
+            vstruct = _lib.VNorm(_f(vc.lookup_table2, "lookup_table2"), 1.0, 0.0, 0, 0)
+            ly.vnorm = ctypes.pointer(vstruct)
+    return ly, (vstruct,)
+
+
+def keep_columns(layer, c0, S, keep, device):
+    """kvq_keep_columns: of the S newest compressed columns c0 .. c0+S-1 of the layer (struct from make_layer: K and V in
+    one launch; or from side_layer) keep the n = len(keep) columns c0 + keep[j] -- they move to c0 + j, the S - n columns
+    behind are zero again.  keep: host sequence, strictly ascending, keep[0] == 0, keep[j] < S <= 32.  The caller moves
+    klen / vlen back by S - n."""
+    keep = [int(x) for x in keep]
+    S = int(S)
+    if not 1 <= S <= MAX_TREE:
+        raise ValueError("keep_columns: 1 <= S <= %d, got %d" % (MAX_TREE, S))
+    if not keep or keep[0] != 0:
+        raise ValueError("keep_columns: keep[0] must be 0 (the root stays), got %r" % (keep[:1],))
+    if any(b <= a for a, b in zip(keep, keep[1:])) or keep[-1] >= S:
+        raise ValueError("keep_columns: keep must be strictly ascending with entries < S = %d, got %r" % (S, keep))
+    arr = _host_bytes(keep, "keep", len(keep))
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(idx):
+        _lib.check(_L().kvq_keep_columns(ctypes.byref(layer), int(c0), S, arr, len(keep), _stream()), "kvq_keep_columns")
