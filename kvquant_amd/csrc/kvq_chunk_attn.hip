@@ -15,7 +15,7 @@
 //       rows [max_len][n_out]; ids are global channels);
 //   P3  waves 0-3: RoPE of each (k, k+64) pair at the column's position (sincos_rev, the angle rule of the decode
 //       kernels) -> fp16 K tile in the XOR-swizzled layout of the prefill kernel; waves 4-7: fp16 V^T tile;
-//   then S^T = K.Q^T, mask, online softmax, O^T += V^T.P^T exactly as the prefill kernel.
+//   then the tile step both kernels share (kvq_flash_tile.h): S^T = K.Q^T, mask, online softmax, O^T += V^T.P^T.
 // The fp16 sink tokens (post-RoPE K [Hkv][128][n_sink], V [Hkv][n_sink][128]) are one prefix tile without decode.
 // The causal mask is evaluated only on tiles that reach past the wave's first row (c0 + q0) or past the last column.
 //
@@ -32,31 +32,22 @@
 // TREE): the chunk's rows are the nodes of a tree in topological order (row 0 the root).  Row i sees every column < c0
 // and column c0 + j iff node j is i itself or one of its ancestors (bit j of anc[i]); column c0 + j rotates at the
 // position of its DEPTH, pos_offset + c0 + depth[j], so siblings share a position.  anc / depth ride in the kernel
-// arguments (Tree below).  A chain (parent[i] = i - 1) is the grouped kernel, bit for bit.
+// arguments (Args::tree).  A chain (parent[i] = i - 1) is the grouped kernel, bit for bit.
 //
 // kvq_keep_columns (end of the file): after a tree round the accepted root-to-leaf path moves into contiguous columns
 // -- a copy of packed words, codebook rows and outlier rows; the keys are stored pre-RoPE, nothing is re-rotated.
 #include "kvq_common.h"
+#include "kvq_flash_tile.h"
 #include "kvq_host.h"
 
 namespace kvq {
 namespace chunk {
 
-typedef _Float16 f16;
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace flash;
 
-constexpr int kD = 128;            // head_dim
-constexpr int kQB = 32;            // query rows per wave
 constexpr int kAW = 8;             // waves per workgroup
 constexpr int kThreads = kAW * 64;
 constexpr int kQW = kQB * kAW;     // query rows per workgroup
-constexpr int kKV = 64;            // columns per tile
-constexpr int kKRow = kD * 2;      // bytes of a K row in LDS
-constexpr int kVRow = 136;         // bytes of a V^T row in LDS (64 keys x 2 B + 8 pad)
 constexpr int kSR = kD + 4;        // floats per column of the fp32 stages
 constexpr int kMaxSink = 64;       // the sink tokens fit one tile
 constexpr int kTargetWorkgroups = 512;
@@ -64,6 +55,12 @@ constexpr int kMinTilesPerSplit = 4;
 constexpr int kMaxSplits = 64;
 constexpr int kMaxS = 65536;
 constexpr size_t kMaxWorkspace = size_t(1) << 30;
+
+// TR: the tree of a chunk of S <= 32 rows
+struct Tree {
+  uint32_t anc[kQB];                 // bit j of anc[i]: node j is i or an ancestor of i
+  uint8_t depth[kQB];                // edges from the root (row 0)
+};
 
 struct Args {
   const int32_t *kmat, *vmat;
@@ -80,41 +77,33 @@ struct Args {
   int64_t max_len, c0;
   int Hq, G, S, n_sink, n_out, pos_offset, nqb, nsplit, tps;
   float rope_theta, scale_log2e;
+  const float *rt_freq;              // RT (scaled RoPE, kvq.h: kvq_rope): the K tiles rotate with the frequencies rt_freq
+  float rt_af;                       // [64] and (cos, sin) scaled by rt_af (before the fp16 rounding of the tile)
+  Tree tree;                         // TR only (kernel arguments a variant does not read are never loaded)
 };
 
-// TR: the tree of a chunk of S <= 32 rows, by value in the kernel arguments
-struct Tree {
-  uint32_t anc[kQB];                 // bit j of anc[i]: node j is i or an ancestor of i
-  uint8_t depth[kQB];                // edges from the root (row 0)
-};
-
-__device__ __forceinline__ uint32_t pack_f16(float a, float b) {
-  uint32_t r;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// RT (scaled RoPE, kvq.h: kvq_rope): the K tiles rotate with the frequencies rt_freq [64] and (cos, sin) scaled by the
-// attention factor rt_af (before the fp16 rounding of the tile); chunk_attn_kernel_rt below
-// (the LDS arrays are the kernels' own, declared by KVQ_CHUNK_LDS)
-#define KVQ_CHUNK_LDS                                                  \
-  __shared__ float klut[kD * (1 << BITS)];                             \
-  __shared__ float theta[64];                                          \
-  __shared__ float vrow[kKV * ((1 << BITS) + 1)];                      \
-  __shared__ __attribute__((aligned(16))) float kst[kKV * kSR];        \
-  __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];        \
-  __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow]; \
-  __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
-// TR (with GR only): tree mask and per-node positions from the LDS copies tanc [32] / tdepth [32] of a Tree, which the
-// kernel wrote before the call (chunk_attn_tree_kernel below; the barriers in front of the first use order them)
-template <int BITS, bool RT, bool GR = false, bool TR = false>
-__device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, float *theta, float *vrow, float *kst,
-                                                float *vst, unsigned char *k16, unsigned char *vt16, const float *rt_freq,
-                                                float rt_af, const uint32_t *tanc = nullptr,
-                                                const int *tdepth = nullptr) {
+// One kernel for the per-head (GR = TR = false), grouped (GR) and tree (GR and TR) geometries.  TR: tree mask and per-node
+// positions from LDS copies of a.tree (the barriers in front of the first use order them).
+template <int BITS, bool RT, bool GR, bool TR>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
   static_assert(!TR || GR, "the tree variant runs in the grouped geometry");
   constexpr int N = 1 << BITS;
   constexpr int WPH = kD / 32 * BITS;
+  __shared__ float klut[kD * N];
+  __shared__ float theta[64];
+  __shared__ float vrow[kKV * (N + 1)];
+  __shared__ __attribute__((aligned(16))) float kst[kKV * kSR];
+  __shared__ __attribute__((aligned(16))) float vst[kKV * kSR];
+  __shared__ __attribute__((aligned(16))) unsigned char k16[kKV * kKRow];
+  __shared__ __attribute__((aligned(16))) unsigned char vt16[kD * kVRow];
+  __shared__ uint32_t tanc[kQB];                       // TR only (unused LDS is not allocated)
+  __shared__ int tdepth[kQB];
+  if constexpr (TR) {
+    if (threadIdx.x < kQB) {
+      tanc[threadIdx.x] = a.tree.anc[threadIdx.x];
+      tdepth[threadIdx.x] = a.tree.depth[threadIdx.x];
+    }
+  }
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hi = lane >> 5, ql = lane & 31;
@@ -146,41 +135,19 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
   const bool with_sinks = split == 0 && a.n_sink > 0;
 
   for (int e = tid; e < kD * N; e += kThreads) klut[e] = a.klut[(int64_t)hk * kD * N + e];
-  if (tid < 64) theta[tid] = RT ? rt_freq[tid] : rope_freq(a.rope_theta, tid);
+  if (tid < 64) theta[tid] = RT ? a.rt_freq[tid] : rope_freq(a.rope_theta, tid);
 
-  // ---- Q fragments (B operand of S^T): lane (q, hi) holds Q[q][ks*16 + hi*8 .. +7]
   f16x8 qf[8];
-  {
-    const f16 *qp = a.q + (int64_t)h * a.qsh + (int64_t)qrc * a.qss + hi * 8;
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) qf[ks] = *reinterpret_cast<const f16x8 *>(qp + ks * 16);
-  }
+  load_q(a.q + (int64_t)h * a.qsh + (int64_t)qrc * a.qss, hi, qf);
   f32x16 oacc[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) oacc[i][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
+  float m_run, l_run;
+  reset(oacc, m_run, l_run);
 
   // ---- S^T, mask, online softmax, O^T of one staged tile.  sink: key j of the tile is sink token j (no causal mask);
   // else key j is compressed column t0 + j, visible to row q iff t0 + j <= c0 + q (and < Lc); TR: iff t0 + j < c0 or
   // node t0 + j - c0 is in the row's ancestor set (which has no bit at or above S)
   auto attend_tile = [&](bool sink, int64_t t0) __attribute__((always_inline)) {
-    const bool active = has_rows && q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1);
-    if (!active) return;
-    f32x16 sacc[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; kb++) {
-#pragma unroll
-      for (int r = 0; r < 16; r++) sacc[kb][r] = 0.f;
-      const int key = kb * 32 + ql;
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++) {
-        const int c = kk * 2 + hi;
-        const f16x8 kf = *reinterpret_cast<const f16x8 *>(k16 + key * kKRow + ((c ^ (key & 15)) << 4));
-        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sacc[kb], 0, 0, 0);
-      }
-    }
+    if (!(has_rows && q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1))) return;
     const bool diag = sink ? a.n_sink < kKV : TR ? t0 + kKV > a.c0 : (t0 + kKV - 1 > a.c0 + q0 || t0 + kKV > Lc);
     // TR: bit j of vism[kb] = key kb * 32 + 4 * hi + j of the tile is visible to this lane's row (rows >= S: no node)
     uint32_t vism[2] = {0u, 0u};
@@ -193,67 +160,13 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
         vism[1] = (uint32_t)(m >> 32) >> (4 * hi);
       }
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        float s = sacc[kb][r];
-        if (diag) {
-          const int j = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          bool vis;
-          if constexpr (TR) {
-            vis = sink ? j < a.n_sink : (vism[kb] >> ((r & 3) + 8 * (r >> 2))) & 1u;
-          } else {
-            vis = sink ? j < a.n_sink : (t0 + j <= a.c0 + qrow && t0 + j < Lc);
-          }
-          if (!vis) s = -INFINITY;
-          sacc[kb][r] = s;
-        }
-        mx = fmaxf(mx, s);
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);
-    const float m_use = m_new == -INFINITY ? 0.f : m_new;
-    const float mc = -m_use * a.scale_log2e;
-    float ps = 0.f;
-    uint32_t pp[2][8];
-#pragma unroll
-    for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], a.scale_log2e, mc));
-        const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r + 1], a.scale_log2e, mc));
-        ps += p0 + p1;
-        pp[kb][r >> 1] = pack_f16(p0, p1);
-      }
-    ps += __shfl_xor(ps, 32);
-    if (__any(m_new != m_run)) {
-      const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * a.scale_log2e);
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) oacc[i][r] *= alpha;
-    }
-    l_run += ps;
-    m_run = m_new;
-#pragma unroll
-    for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-      for (int ks2 = 0; ks2 < 2; ks2++) {
-        const u32x4 pw = {pp[kb][ks2 * 4], pp[kb][ks2 * 4 + 1], pp[kb][ks2 * 4 + 2], pp[kb][ks2 * 4 + 3]};
-        const f16x8 pf = __builtin_bit_cast(f16x8, pw);
-        const int kofs = (kb * 32 + ks2 * 16 + 4 * hi) * 2;
-#pragma unroll
-        for (int db = 0; db < 4; db++) {
-          const unsigned char *row = vt16 + (db * 32 + ql) * kVRow + kofs;
-          const f16x4 v0 = *reinterpret_cast<const f16x4 *>(row);
-          const f16x4 v1 = *reinterpret_cast<const f16x4 *>(row + 16);
-          const f16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[db], 0, 0, 0);
-        }
-      }
+    tile_step(k16, vt16, qf, oacc, m_run, l_run, a.scale_log2e, diag, hi, ql,
+              [&](int kb, int r) __attribute__((always_inline)) -> bool {
+                const int j = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                if (sink) return j < a.n_sink;
+                if constexpr (TR) return (vism[kb] >> ((r & 3) + 8 * (r >> 2))) & 1u;
+                else return t0 + j <= a.c0 + qrow && t0 + j < Lc;
+              });
   };
 
   // ---- the sink tokens: one prefix tile, fp16 as stored (keys past n_sink are zero and masked)
@@ -342,8 +255,8 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
         float sn, cs;
         sincos_rev(theta[j] * posf, sn, cs);
         if constexpr (RT) {
-          sn *= rt_af;
-          cs *= rt_af;
+          sn *= a.rt_af;
+          cs *= a.rt_af;
         }
         const float klo = kr[j], khi = kr[j + 64];
         lo[i] = fmaf(cs, klo, -(sn * khi));
@@ -387,54 +300,6 @@ __device__ __forceinline__ void chunk_attn_body(const Args &a, float *klut, floa
     }
   }
 }
-
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
-  KVQ_CHUNK_LDS
-  chunk_attn_body<BITS, false>(a, klut, theta, vrow, kst, vst, k16, vt16, nullptr, 1.f);
-}
-
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel_rt(Args a, const float *rt_freq, float rt_af) {
-  KVQ_CHUNK_LDS
-  chunk_attn_body<BITS, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af);
-}
-
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_grouped_kernel(Args a) {
-  KVQ_CHUNK_LDS
-  chunk_attn_body<BITS, false, true>(a, klut, theta, vrow, kst, vst, k16, vt16, nullptr, 1.f);
-}
-
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_grouped_kernel_rt(Args a, const float *rt_freq, float rt_af) {
-  KVQ_CHUNK_LDS
-  chunk_attn_body<BITS, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af);
-}
-// the tree kernels' LDS copies of their Tree argument
-#define KVQ_CHUNK_TREE_LDS                   \
-  __shared__ uint32_t tanc[kQB];             \
-  __shared__ int tdepth[kQB];                \
-  if (threadIdx.x < kQB) {                   \
-    tanc[threadIdx.x] = tr.anc[threadIdx.x]; \
-    tdepth[threadIdx.x] = tr.depth[threadIdx.x]; \
-  }
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_tree_kernel(Args a, Tree tr) {
-  KVQ_CHUNK_LDS
-  KVQ_CHUNK_TREE_LDS
-  chunk_attn_body<BITS, false, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, nullptr, 1.f, tanc, tdepth);
-}
-
-template <int BITS>
-__global__ __launch_bounds__(kThreads, 1) void chunk_attn_tree_kernel_rt(Args a, Tree tr, const float *rt_freq,
-                                                                         float rt_af) {
-  KVQ_CHUNK_LDS
-  KVQ_CHUNK_TREE_LDS
-  chunk_attn_body<BITS, true, true, true>(a, klut, theta, vrow, kst, vst, k16, vt16, rt_freq, rt_af, tanc, tdepth);
-}
-#undef KVQ_CHUNK_LDS
-#undef KVQ_CHUNK_TREE_LDS
 
 // out[s][h][:] = sum_split w * O_split / sum_split w * l_split, w = 2^((m_split - M) * c), splits in index order
 __global__ __launch_bounds__(kD) void chunk_attn_merge_kernel(const float *__restrict__ part_o,
@@ -519,8 +384,8 @@ static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0
                                   float *out, void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream,
                                   bool grouped, const uint8_t *parent = nullptr) {
   if (!ly || !q || !out || !rope_ok(rope)) return KVQ_EINVAL;
-  chunk::Tree tree;
-  if (parent && !(grouped && tree_of(parent, S, tree))) return KVQ_EINVAL;
+  chunk::Args a = {};
+  if (parent && !(grouped && tree_of(parent, S, a.tree))) return KVQ_EINVAL;
   const int bits = ly->bits;
   if ((bits != 2 && bits != 3 && bits != 4) || ly->hd != chunk::kD || ly->thr_k <= 0) return KVQ_EINVAL;
   chunk::Plan p;
@@ -540,7 +405,6 @@ static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0
     return KVQ_EINVAL;
   if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < p.o_bytes + p.ml_bytes)
     return KVQ_EWORKSPACE;
-  chunk::Args a;
   a.kmat = ly->kmat;
   a.vmat = ly->vmat;
   a.klut = klut;
@@ -569,39 +433,18 @@ static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0
   a.tps = p.tps;
   a.rope_theta = ly->rope_theta;
   a.scale_log2e = (1.0f / sqrtf((float)chunk::kD)) * 1.4426950408889634f;
+  a.rt_freq = rope ? rope->inv_freq : nullptr;
+  a.rt_af = rope ? rope->attention_factor : 1.f;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((int64_t)(grouped ? ly->H : Hq * p.nqb) * p.nsplit)), block(chunk::kThreads);
-  if (parent && rope) {
-    const float *f = rope->inv_freq;
-    const float af = rope->attention_factor;
-    if (bits == 4) chunk::chunk_attn_tree_kernel_rt<4><<<grid, block, 0, st>>>(a, tree, f, af);
-    else if (bits == 3) chunk::chunk_attn_tree_kernel_rt<3><<<grid, block, 0, st>>>(a, tree, f, af);
-    else chunk::chunk_attn_tree_kernel_rt<2><<<grid, block, 0, st>>>(a, tree, f, af);
-  } else if (parent) {
-    if (bits == 4) chunk::chunk_attn_tree_kernel<4><<<grid, block, 0, st>>>(a, tree);
-    else if (bits == 3) chunk::chunk_attn_tree_kernel<3><<<grid, block, 0, st>>>(a, tree);
-    else chunk::chunk_attn_tree_kernel<2><<<grid, block, 0, st>>>(a, tree);
-  } else if (grouped && rope) {
-    const float *f = rope->inv_freq;
-    const float af = rope->attention_factor;
-    if (bits == 4) chunk::chunk_attn_grouped_kernel_rt<4><<<grid, block, 0, st>>>(a, f, af);
-    else if (bits == 3) chunk::chunk_attn_grouped_kernel_rt<3><<<grid, block, 0, st>>>(a, f, af);
-    else chunk::chunk_attn_grouped_kernel_rt<2><<<grid, block, 0, st>>>(a, f, af);
-  } else if (grouped) {
-    if (bits == 4) chunk::chunk_attn_grouped_kernel<4><<<grid, block, 0, st>>>(a);
-    else if (bits == 3) chunk::chunk_attn_grouped_kernel<3><<<grid, block, 0, st>>>(a);
-    else chunk::chunk_attn_grouped_kernel<2><<<grid, block, 0, st>>>(a);
-  } else if (rope) {
-    const float *f = rope->inv_freq;
-    const float af = rope->attention_factor;
-    if (bits == 4) chunk::chunk_attn_kernel_rt<4><<<grid, block, 0, st>>>(a, f, af);
-    else if (bits == 3) chunk::chunk_attn_kernel_rt<3><<<grid, block, 0, st>>>(a, f, af);
-    else chunk::chunk_attn_kernel_rt<2><<<grid, block, 0, st>>>(a, f, af);
-  } else {
-    if (bits == 4) chunk::chunk_attn_kernel<4><<<grid, block, 0, st>>>(a);
-    else if (bits == 3) chunk::chunk_attn_kernel<3><<<grid, block, 0, st>>>(a);
-    else chunk::chunk_attn_kernel<2><<<grid, block, 0, st>>>(a);
-  }
+  with_bits(bits, [&](auto B) {
+    with_int<0, 1, 2>(parent ? 2 : grouped ? 1 : 0, [&](auto V) {       // per-head, grouped, tree
+      with_bool(rope != nullptr, [&](auto RT) {
+        constexpr int v = decltype(V)::value;
+        chunk::chunk_attn_kernel<decltype(B)::value, decltype(RT)::value, v >= 1, v == 2><<<grid, block, 0, st>>>(a);
+      });
+    });
+  });
   int rc = check_launch();
   if (rc) return rc;
   chunk::chunk_attn_merge_kernel<<<(unsigned)((int64_t)S * Hq), chunk::kD, 0, st>>>(a.part_o, a.part_ml, out, Hq, S,

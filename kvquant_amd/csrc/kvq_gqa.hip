@@ -358,44 +358,10 @@ static void gqa_mix_plan(int Hkv, int64_t L, int &n_chunks, int64_t &ct) {
   n_chunks = (int)((L + ct - 1) / ct);
 }
 
-template <int BITS>
-static int launch_score(int GB, dim3 grid, dim3 block, size_t lds, hipStream_t st, const uint32_t *mat, const float *lut,
-                        const float *qp, const float *q32, const float *out_t, const int32_t *idx_t, float *mul,
-                        float *parts, int64_t L, int64_t max_len, int Hkv, int G, int hpw, int n_out, int pos_offset,
-                        float theta, float inv, int n_parts, const kvq_rope *rope) {
-#define KVQ_GQA_SCORE(B)                                                                                              \
-  if (rope)                                                                                                           \
-    gqa_score_kernel_rt<BITS, B><<<grid, block, lds, st>>>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv, \
-                                                           G, hpw, n_out, pos_offset, inv, n_parts, rope->inv_freq,      \
-                                                           rope->attention_factor);                                      \
-  else                                                                                                                \
-    gqa_score_kernel<BITS, B><<<grid, block, lds, st>>>(mat, lut, qp, q32, out_t, idx_t, mul, parts, L, max_len, Hkv,   \
-                                                        G, hpw, n_out, pos_offset, theta, inv, n_parts)
-  switch (GB) {
-    case 1: KVQ_GQA_SCORE(1); break;
-    case 2: KVQ_GQA_SCORE(2); break;
-    case 4: KVQ_GQA_SCORE(4); break;
-    default: KVQ_GQA_SCORE(8); break;
-  }
-#undef KVQ_GQA_SCORE
-  return check_launch();
-}
-
-template <int BITS>
-static int launch_mix(int GB, dim3 grid, hipStream_t st, const float *p, const uint32_t *mat, const float *lut_rows,
-                      const float *vout, const int32_t *vidx, float *dst, int64_t L, int64_t max_len, int64_t ct, int Hq,
-                      int G, int n_out, int accumulate, int n_chunks) {
-#define KVQ_GQA_MIX(B)                                                                                              \
-  gqa_mix_kernel<BITS, B><<<grid, 256, 0, st>>>(p, mat, lut_rows, vout, vidx, dst, L, max_len, ct, Hq, G, n_out, \
-                                                accumulate, n_chunks)
-  switch (GB) {
-    case 1: KVQ_GQA_MIX(1); break;
-    case 2: KVQ_GQA_MIX(2); break;
-    case 4: KVQ_GQA_MIX(4); break;
-    default: KVQ_GQA_MIX(8); break;
-  }
-#undef KVQ_GQA_MIX
-  return check_launch();
+// the G buckets the kernels are instantiated for (gqa_bucket)
+template <class F>
+static void with_gb(int GB, F &&f) {
+  with_int<8, 4, 2, 1>(GB, f);
 }
 
 }  // namespace kvq
@@ -440,12 +406,9 @@ int kvq_score_k_gqa_rope(int bits, const void *q, int q_is_half, const int32_t *
   float *q32 = reinterpret_cast<float *>(workspace);
   float *qp = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) + gqa_q32_bytes(Hq));
   const int nprep = Hkv * kHeadDim * GB;
-  switch (GB) {
-    case 1: gqa_qprep_kernel<1><<<(nprep + 255) / 256, 256, 0, st>>>(q, q_is_half, q32, qp, Hq, Hkv, G); break;
-    case 2: gqa_qprep_kernel<2><<<(nprep + 255) / 256, 256, 0, st>>>(q, q_is_half, q32, qp, Hq, Hkv, G); break;
-    case 4: gqa_qprep_kernel<4><<<(nprep + 255) / 256, 256, 0, st>>>(q, q_is_half, q32, qp, Hq, Hkv, G); break;
-    default: gqa_qprep_kernel<8><<<(nprep + 255) / 256, 256, 0, st>>>(q, q_is_half, q32, qp, Hq, Hkv, G); break;
-  }
+  with_gb(GB, [&](auto B) {
+    gqa_qprep_kernel<decltype(B)::value><<<(nprep + 255) / 256, 256, 0, st>>>(q, q_is_half, q32, qp, Hq, Hkv, G);
+  });
   int rc = check_launch();
   if (rc) return rc;
   int hpw, nw;
@@ -455,14 +418,20 @@ int kvq_score_k_gqa_rope(int bits, const void *q, int q_is_half, const int32_t *
   const size_t lds = (size_t)hpw * kHeadDim * (1u << bits) * 4;
   const uint32_t *m = reinterpret_cast<const uint32_t *>(mat);
   const int np = softmax_parts ? n_parts : 0;
-  if (bits == 4)
-    return launch_score<4>(GB, grid, block, lds, st, m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
-                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np, rope);
-  if (bits == 3)
-    return launch_score<3>(GB, grid, block, lds, st, m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
-                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np, rope);
-  return launch_score<2>(GB, grid, block, lds, st, m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
-                         max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd, np, rope);
+  with_bits(bits, [&](auto BITS) {
+    with_gb(GB, [&](auto B) {
+      constexpr int bt = decltype(BITS)::value, gb = decltype(B)::value;
+      if (rope)
+        gqa_score_kernel_rt<bt, gb><<<grid, block, lds, st>>>(m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts,
+                                                              L, max_len, Hkv, G, hpw, n_out, pos_offset, inv_sqrt_hd, np,
+                                                              rope->inv_freq, rope->attention_factor);
+      else
+        gqa_score_kernel<bt, gb><<<grid, block, lds, st>>>(m, lut, qp, q32, outliers_t, outlier_idx_t, mul, softmax_parts, L,
+                                                           max_len, Hkv, G, hpw, n_out, pos_offset, rope_theta, inv_sqrt_hd,
+                                                           np);
+    });
+  });
+  return check_launch();
 }
 
 size_t kvq_mix_v_gqa_workspace_bytes(int bits, int Hq, int Hkv, int hd, int64_t L) {
@@ -489,13 +458,13 @@ int kvq_mix_v_gqa(int bits, const float *p, const int32_t *mat, float *mul, cons
   float *dst = n_chunks == 1 ? mul : reinterpret_cast<float *>(workspace);
   dim3 grid((unsigned)n_chunks, (unsigned)Hkv);
   const uint32_t *m = reinterpret_cast<const uint32_t *>(mat);
-  int rc;
-  if (bits == 4)
-    rc = launch_mix<4>(GB, grid, st, p, m, lut_rows, outliers, outlier_idx, dst, L, max_len, ct, Hq, G, n_out, accumulate, n_chunks);
-  else if (bits == 3)
-    rc = launch_mix<3>(GB, grid, st, p, m, lut_rows, outliers, outlier_idx, dst, L, max_len, ct, Hq, G, n_out, accumulate, n_chunks);
-  else
-    rc = launch_mix<2>(GB, grid, st, p, m, lut_rows, outliers, outlier_idx, dst, L, max_len, ct, Hq, G, n_out, accumulate, n_chunks);
+  with_bits(bits, [&](auto BITS) {
+    with_gb(GB, [&](auto B) {
+      gqa_mix_kernel<decltype(BITS)::value, decltype(B)::value><<<grid, 256, 0, st>>>(
+          p, m, lut_rows, outliers, outlier_idx, dst, L, max_len, ct, Hq, G, n_out, accumulate, n_chunks);
+    });
+  });
+  const int rc = check_launch();
   if (rc || n_chunks == 1) return rc;
   const int n = Hq * kHeadDim;
   gqa_mix_reduce_kernel<<<(n + 255) / 256, 256, 0, st>>>(dst, mul, n, n_chunks, accumulate);

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/kvq.h"
 
 namespace kvq {
@@ -24,6 +26,23 @@ inline int check_launch() {
     return KVQ_ELAUNCH;
   }
   return KVQ_OK;
+}
+
+// Run-time value -> template argument (the host-side companion of static_for): with_int<2, 3, 4>(v, f) calls
+// f(std::integral_constant<int, B>{}) for the listed B that equals v (and returns false for a v not listed), so a
+// launch site names its kernel and arguments once and the list spells the instantiation set.
+template <int... Bs, class F>
+inline bool with_int(int v, F &&f) {
+  return ((v == Bs ? (f(std::integral_constant<int, Bs>{}), true) : false) || ...);
+}
+template <class F>
+inline bool with_bits(int bits, F &&f) {
+  return with_int<2, 3, 4>(bits, f);
+}
+template <class F>
+inline void with_bool(bool b, F &&f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 // kvq_append.hip: packed codes of S prompt tokens of K (no rescaled output)

@@ -3,39 +3,23 @@
 // this is a flash-style kernel written for gfx950: fp16 inputs, fp32 accumulation on
 // v_mfma_f32_32x32x16_f16, online softmax, no S x S matrix in memory.
 //
-// Decomposition: workgroup = 4 waves = 128 query rows of one head; wave = 32 query rows (its Q fragments live
-// in registers for the whole kernel); keys / values arrive in 64-key tiles shared by the four waves through LDS
-// (double buffered, one barrier per tile).  Both products are computed TRANSPOSED so that a lane owns ONE
-// query row end to end (column = lane & 31 of every accumulator):
-//   S^T[key][q] = K[key][:] . Q[q][:]      A = K tile (LDS, 16-byte rows chunks XOR-swizzled by the key: conflict
-//                                          free ds_read_b128), B = Q (registers)
-//   O^T[d][q]  += V^T[d][key] . P^T[key][q]  A = V^T tile (LDS, transposed while staging, row stride 136 B:
-//                                          conflict free ds_read_b64), B = P packed to fp16 IN PLACE: the MFMA
-//                                          summation index is just a label, so the keys are fed in the order the
-//                                          S^T accumulator holds them (rows (r&3) + 8(r>>2) + 4(lane>>5)) and the
-//                                          V^T fragment is read in the same order -- no cross-lane exchange.
-// Row max / sum: in-lane over the lane's 32 scores of the tile + one exchange with lane ^ 32.
+// Decomposition: workgroup = 8 waves = 256 query rows of one head; wave = 32 query rows; keys / values arrive in
+// 64-key tiles shared by the waves through LDS (double buffered, one barrier per tile) in the layouts of the tile step
+// (kvq_flash_tile.h: the transposed products, the online softmax).
 // Causal mask only on the tiles that cross the diagonal; heavy (late) query blocks are scheduled first.
 #include "kvq_common.h"
+#include "kvq_flash_tile.h"
 #include "kvq_host.h"
 
 namespace kvq {
 
-typedef _Float16 f16;
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace flash;
 
-constexpr int kD = 128;          // head_dim
-constexpr int kQB = 32;          // query rows per wave
 #ifndef KVQ_ATTN_WAVES
 #define KVQ_ATTN_WAVES 8
 #endif
 constexpr int kAW = KVQ_ATTN_WAVES;           // waves per workgroup
 constexpr int kQW = kQB * kAW;   // query rows per workgroup
-constexpr int kKV = 64;          // keys per tile
-constexpr int kKRow = kD * 2;    // bytes of a K row in LDS
-constexpr int kVRow = 136;       // bytes of a V^T row in LDS (64 keys x 2 B + 8 pad)
 constexpr int kKTile = kKV * kKRow;      // 16384
 constexpr int kVTile = kD * kVRow;       // 17408
 constexpr int kStage = kKTile + kVTile;  // 33792
@@ -49,16 +33,8 @@ struct AttnArgs {
   int G;                  // GQA: query heads per KV head (the GQA instantiation reads K / V of head h / G)
 };
 
-// two floats -> packed fp16, ROUND TO NEAREST (gfx950's v_cvt_pk_f16_f32; cvt_pkrtz truncates, which biases P -- and
-// with it every output -- down by 2^-12 .. 2^-11 relative to the unrounded row sum it is normalised with)
-__device__ __forceinline__ uint32_t pack_f16(float a, float b) {
-  uint32_t r;
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
 template <bool GQA>
-__global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kernel(AttnArgs a) {
+__global__ __launch_bounds__(kAW * 64, 2) void prefill_attn_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * kStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hi = lane >> 5, ql = lane & 31;
@@ -74,20 +50,11 @@ __global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kerne
   const f16 *kh = a.k + (int64_t)hk * a.ksh;
   const f16 *vh = a.v + (int64_t)hk * a.vsh;
 
-  // ---- Q fragments (B operand of S^T): lane (q, hi) holds Q[q][ks*16 + hi*8 .. +7], ks = 0..7
   f16x8 qf[8];
-  {
-    const f16 *qp = a.q + (int64_t)h * a.qsh + (int64_t)qrc * a.qss + hi * 8;
-#pragma unroll
-    for (int ks = 0; ks < 8; ks++) qf[ks] = *reinterpret_cast<const f16x8 *>(qp + ks * 16);
-  }
-
+  load_q(a.q + (int64_t)h * a.qsh + (int64_t)qrc * a.qss, hi, qf);
   f32x16 oacc[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int r = 0; r < 16; r++) oacc[i][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
+  float m_run, l_run;
+  reset(oacc, m_run, l_run);
 
   const int kv_end = (q0w + kQW < a.S ? q0w + kQW : a.S);     // keys [0, kv_end) matter to this workgroup
   const int n_tiles = (kv_end + kKV - 1) / kKV;
@@ -95,7 +62,6 @@ __global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kerne
   // ---- staging: thread -> (key = tid & 63, 16-byte chunks c = (tid >> 6) + kAW j, j < 16 / kAW) of K and V
   constexpr int NCH = 16 / kAW;
   const int skey = tid & 63, sc0 = tid >> 6;
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));     // (a native vector: HIP's uint4 class ends up on the stack here)
   u32x4 kreg[NCH], vreg[NCH];
   auto load_tile = [&](int t) __attribute__((always_inline)) {
     int key = t * kKV + skey;
@@ -132,87 +98,14 @@ __global__ __launch_bounds__(kAW * 64, kAW == 8 ? 2 : 2) void prefill_attn_kerne
     if (t + 1 < n_tiles) load_tile(t + 1);               // in flight during the math
     const int key0 = t * kKV;
     // a wave whose rows all lie before this tile has nothing to add (causal); it still takes part in the staging
-    const bool active = key0 <= q0 + kQB - 1;
-    if (active) {
+    if (key0 <= q0 + kQB - 1) {
       const unsigned char *ks = smem + stage * kStage;
-      const unsigned char *vs = ks + kKTile;
-      // ---- S^T = K . Q^T: two 32-key blocks
-      f32x16 sacc[2];
-#pragma unroll
-      for (int kb = 0; kb < 2; kb++) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) sacc[kb][r] = 0.f;
-        const int key = kb * 32 + ql;                      // A operand row of this lane
-#pragma unroll
-        for (int kk = 0; kk < 8; kk++) {
-          const int c = kk * 2 + hi;                       // 16-byte chunk: d = kk*16 + hi*8 .. +7
-          const f16x8 kf = *reinterpret_cast<const f16x8 *>(ks + key * kKRow + ((c ^ (key & 15)) << 4));
-          sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], sacc[kb], 0, 0, 0);
-        }
-      }
-      // ---- mask + scale + online softmax.  Accumulator reg r of block kb: key = key0 + kb*32 + (r&3) + 8(r>>2) + 4hi
       const bool diag = key0 + kKV - 1 > q0 || key0 + kKV > a.S;       // tile crosses the diagonal / the end
-      // (running max m_run is kept in RAW score units; the softmax scale (> 0) and log2(e) are folded into one FMA
-      //  per exponential: p = 2^(s*c - m*c))
-      float mx = -INFINITY;
-#pragma unroll
-      for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          float s = sacc[kb][r];
-          if (diag) {
-            const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-            if (key > qrow || key >= a.S) s = -INFINITY;
-            sacc[kb][r] = s;
-          }
-          mx = fmaxf(mx, s);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float m_new = fmaxf(m_run, mx);
-      const float m_use = m_new == -INFINITY ? 0.f : m_new;            // (a fully masked row so far)
-      const float mc = -m_use * a.scale_log2e;
-      float ps = 0.f;
-      uint32_t pp[2][8];                                                // P^T packed: regs (2i, 2i+1)
-#pragma unroll
-      for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const float p0 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], a.scale_log2e, mc));
-          const float p1 = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r + 1], a.scale_log2e, mc));
-          ps += p0 + p1;
-          pp[kb][r >> 1] = pack_f16(p0, p1);
-        }
-      ps += __shfl_xor(ps, 32);
-      // the running sums only need rescaling when some row's maximum moved (wave-uniform test: rare after the first
-      // tiles on real data); 2^-inf = 0 on the first tile
-      if (__any(m_new != m_run)) {
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_use) * a.scale_log2e);
-        l_run *= alpha;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-          for (int r = 0; r < 16; r++) oacc[i][r] *= alpha;
-      }
-      l_run += ps;
-      m_run = m_new;
-      // ---- O^T += V^T . P^T.  k index (hi*8 + i) of step (kb, ks) stands for key kb*32 + ks*16 + (i>>2)*8 + 4hi + (i&3)
-#pragma unroll
-      for (int kb = 0; kb < 2; kb++)
-#pragma unroll
-        for (int ks2 = 0; ks2 < 2; ks2++) {
-          typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-          const u32x4 pw = {pp[kb][ks2 * 4], pp[kb][ks2 * 4 + 1], pp[kb][ks2 * 4 + 2], pp[kb][ks2 * 4 + 3]};
-          const f16x8 pf = __builtin_bit_cast(f16x8, pw);
-          const int kofs = (kb * 32 + ks2 * 16 + 4 * hi) * 2;          // byte offset of the first 4 keys in a V^T row
-#pragma unroll
-          for (int db = 0; db < 4; db++) {
-            const unsigned char *row = vs + (db * 32 + ql) * kVRow + kofs;
-            const f16x4 v0 = *reinterpret_cast<const f16x4 *>(row);
-            const f16x4 v1 = *reinterpret_cast<const f16x4 *>(row + 16);
-            const f16x8 vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[db], 0, 0, 0);
-          }
-        }
+      tile_step(ks, ks + kKTile, qf, oacc, m_run, l_run, a.scale_log2e, diag, hi, ql,
+                [&](int kb, int r) __attribute__((always_inline)) {
+                  const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                  return key <= qrow && key < a.S;
+                });
     }
     if (t + 1 < n_tiles) store_tile(1 - stage);     // the other stage: free since the barrier of the previous tile
     __syncthreads();

@@ -840,55 +840,76 @@ def chunk_attention_route(Hq, Hkv, S):
     return "heads"
 
 
-def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=None):
-    """kvq_chunk_attention: query i of q (fp16 [Hq, S, 128] view, contiguous last dimension; RoPE'd at position
-    pos_offset + c0 + i) over the fp16 sink tokens and the compressed columns [0, c0 + i] of the layer (struct from
-    make_layer, layer.H = KV heads; the chunk must already be packed into columns c0 .. c0+S-1).  k_sink fp16
-    [Hkv, 128, n_sink] (post-RoPE) / v_sink fp16 [Hkv, n_sink, 128], or None.  Returns out f32 [S, Hq, 128].
-    Shapes chunk_attention_route() sends to "grouped" run kvq_chunk_attention_grouped (same arguments and semantics)."""
+def _chunk_call(what, name, layer, Hq, c0, q, out, k_sink, v_sink, rope, parent=None):
+    """the q / sink checks, output, workspace and call that chunk_attention and chunk_attention_tree share: runs the
+    library's <name>_rope (workspace from <name>_workspace_bytes; name None: by chunk_attention_route); parent: the tree
+    entry's extra argument"""
     if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float16 and q.dim() == 3 and q.stride(2) == 1):
         raise ValueError("q: expected an fp16 GPU tensor [Hq, S, 128] with a contiguous last dimension")
     if q.shape[0] != Hq or q.shape[2] != 128:
         raise ValueError("q: expected [%d, S, 128], got %s" % (Hq, tuple(q.shape)))
     if (k_sink is None) != (v_sink is None):
         raise ValueError("k_sink and v_sink come together")
-    S = q.shape[1]
+    S = int(q.shape[1])
+    extra = ()
+    if parent is not None:
+        if len(parent) != S:
+            raise ValueError("%s: %d rows, parent has %d entries" % (what, S, len(parent)))
+        extra = (parent if isinstance(parent, ctypes.Array) else tree_parent_array(parent),)
     n_sink = 0 if k_sink is None else int(k_sink.shape[2])
     if out is None:
         out = torch.empty((S, Hq, 128), dtype=torch.float32, device=q.device)
     with _Dev(out):
-        name = "kvq_chunk_attention_grouped" if chunk_attention_route(Hq, layer.H, S) == "grouped" else "kvq_chunk_attention"
-        nbytes = getattr(_L(), name + "_workspace_bytes")(int(Hq), layer.H, int(S), int(c0))
+        if name is None:
+            name = "kvq_chunk_attention_grouped" if chunk_attention_route(Hq, layer.H, S) == "grouped" else "kvq_chunk_attention"
+        nbytes = getattr(_L(), name + "_workspace_bytes")(int(Hq), layer.H, S, int(c0))
         if nbytes == 0:
-            raise ValueError("chunk_attention: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
+            raise ValueError("%s: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (what, Hq, layer.H, S, c0))
         base, usable, ws = _aligned_workspace(out.device, nbytes, "chunk")
         _lib.check(getattr(_L(), name + "_rope")(
-            ctypes.byref(layer), int(Hq), int(S), int(c0), q.data_ptr(), q.stride(0), q.stride(1),
+            ctypes.byref(layer), int(Hq), S, int(c0), q.data_ptr(), q.stride(0), q.stride(1),
             None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
             None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
-            base, usable, _rope(rope, out.device), _stream()), name + "_rope")
+            base, usable, *extra, _rope(rope, out.device), _stream()), name + "_rope")
     return out
+
+
+def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=None):
+    """kvq_chunk_attention: query i of q (fp16 [Hq, S, 128] view, contiguous last dimension; RoPE'd at position
+    pos_offset + c0 + i) over the fp16 sink tokens and the compressed columns [0, c0 + i] of the layer (struct from
+    make_layer, layer.H = KV heads; the chunk must already be packed into columns c0 .. c0+S-1).  k_sink fp16
+    [Hkv, 128, n_sink] (post-RoPE) / v_sink fp16 [Hkv, n_sink, 128], or None.  Returns out f32 [S, Hq, 128].
+    Shapes chunk_attention_route() sends to "grouped" run kvq_chunk_attention_grouped (same arguments and semantics)."""
+    return _chunk_call("chunk_attention", None, layer, Hq, c0, q, out, k_sink, v_sink, rope)
 
 
 # ---- draft trees: tree mask + per-node positions on the grouped kernel, and the accepted path -------------------------
 MAX_TREE = 32       # rows of a tree chunk (the 32-row block of the grouped kernel), root included
 
 
+def _tree_parents(parent, min_rows, rows):
+    """the one validation pass of a parent array: [0, parent[1], ...] as ints, ValueError unless the tree has
+    min_rows .. MAX_TREE rows and comes in topological order"""
+    S = len(parent)
+    if not min_rows <= S <= MAX_TREE:
+        raise ValueError("a tree chunk has %d .. %d rows (%s), got %d" % (min_rows, MAX_TREE, rows, S))
+    par = [0] * S
+    for i in range(1, S):
+        par[i] = p = int(parent[i])
+        if not 0 <= p < i:
+            raise ValueError("parent[%d] = %d: nodes come in topological order (0 <= parent[i] < i)" % (i, p))
+    return par
+
+
 def tree_tables(parent):
     """(depth, anc) of a tree in topological order, as the library derives them from `parent` (parent[0] is ignored,
     parent[i] < i): depth[0] = 0, depth[i] = depth[parent[i]] + 1; anc[i] = the bit set of i and its ancestors.
     ValueError for a parent array that is no such tree or has more than MAX_TREE rows."""
-    parent = [int(p) for p in parent]
-    S = len(parent)
-    if not 1 <= S <= MAX_TREE:
-        raise ValueError("a tree chunk has 1 .. %d rows (root included), got %d" % (MAX_TREE, S))
-    depth, anc = [0] * S, [1] + [0] * (S - 1)
-    for i in range(1, S):
-        p = parent[i]
-        if not 0 <= p < i:
-            raise ValueError("parent[%d] = %d: nodes come in topological order (0 <= parent[i] < i)" % (i, p))
-        depth[i] = depth[p] + 1
-        anc[i] = anc[p] | (1 << i)
+    par = _tree_parents(list(parent), 1, "root included")
+    depth, anc = [0] * len(par), [1] + [0] * (len(par) - 1)
+    for i in range(1, len(par)):
+        depth[i] = depth[par[i]] + 1
+        anc[i] = anc[par[i]] | (1 << i)
     return depth, anc
 
 
@@ -902,16 +923,8 @@ def _host_bytes(values, name, S):
 def tree_parent_array(parent):
     """the HOST array kvq_chunk_attention_tree takes, from a sequence of S ints (parent[0] is ignored): one pass that
     checks 2 <= S <= MAX_TREE and 0 <= parent[i] < i.  ValueError otherwise."""
-    S = len(parent)
-    if not 2 <= S <= MAX_TREE:
-        raise ValueError("a tree chunk has 2 .. %d rows (root + draft nodes), got %d" % (MAX_TREE, S))
-    arr = (ctypes.c_uint8 * S)()
-    for i in range(1, S):
-        p = int(parent[i])
-        if not 0 <= p < i:
-            raise ValueError("parent[%d] = %d: nodes come in topological order (0 <= parent[i] < i)" % (i, p))
-        arr[i] = p
-    return arr
+    par = _tree_parents(parent, 2, "root + draft nodes")
+    return (ctypes.c_uint8 * len(par))(*par)
 
 
 def chunk_attention_tree(layer, Hq, c0, q, parent, out=None, k_sink=None, v_sink=None, rope=None):
@@ -922,30 +935,8 @@ def chunk_attention_tree(layer, Hq, c0, q, parent, out=None, k_sink=None, v_sink
     pos_offset + c0 + depth[j].  The chunk must already be packed into columns c0 .. c0+S-1 in row order.  Every
     1 <= G <= 8 runs the grouped geometry.  parent may be the array tree_parent_array() made of it (checked there).
     Returns out f32 [S, Hq, 128]."""
-    if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float16 and q.dim() == 3 and q.stride(2) == 1):
-        raise ValueError("q: expected an fp16 GPU tensor [Hq, S, 128] with a contiguous last dimension")
-    if q.shape[0] != Hq or q.shape[2] != 128:
-        raise ValueError("q: expected [%d, S, 128], got %s" % (Hq, tuple(q.shape)))
-    if (k_sink is None) != (v_sink is None):
-        raise ValueError("k_sink and v_sink come together")
-    S = int(q.shape[1])
-    if len(parent) != S:
-        raise ValueError("chunk_attention_tree: %d rows, parent has %d entries" % (S, len(parent)))
-    par = parent if isinstance(parent, ctypes.Array) else tree_parent_array(parent)
-    n_sink = 0 if k_sink is None else int(k_sink.shape[2])
-    if out is None:
-        out = torch.empty((S, Hq, 128), dtype=torch.float32, device=q.device)
-    with _Dev(out):
-        nbytes = _L().kvq_chunk_attention_tree_workspace_bytes(int(Hq), layer.H, S, int(c0))
-        if nbytes == 0:
-            raise ValueError("chunk_attention_tree: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (Hq, layer.H, S, c0))
-        base, usable, ws = _aligned_workspace(out.device, nbytes, "chunk")
-        _lib.check(_L().kvq_chunk_attention_tree_rope(
-            ctypes.byref(layer), int(Hq), S, int(c0), q.data_ptr(), q.stride(0), q.stride(1),
-            None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
-            None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
-            base, usable, par, _rope(rope, out.device), _stream()), "kvq_chunk_attention_tree_rope")
-    return out
+    return _chunk_call("chunk_attention_tree", "kvq_chunk_attention_tree", layer, Hq, c0, q, out, k_sink, v_sink, rope,
+                       parent)
 
 
 def side_layer(kc=None, vc=None):

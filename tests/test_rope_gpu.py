@@ -121,6 +121,33 @@ def test_explicit_theta_table_is_bit_identical(route, bits, sinks, Hkv, G, L, mo
     assert torch.equal(a, b), route
 
 
+@pytest.mark.parametrize("bits", [2, 3, 4])
+@pytest.mark.parametrize("entry", ["heads", "grouped", "tree"])
+def test_explicit_theta_table_is_bit_identical_on_every_chunk_entry(entry, bits, monkeypatch):
+    """every scaled-RoPE instantiation of the chunk kernel (per-head, grouped, tree; 2 / 3 / 4 bit) against its
+    theta-rule twin: S = 7 rows over 60 cached columns (the chunk straddles a 64-column tile with a ragged last tile),
+    G = 4 (rowless waves in the grouped geometry)"""
+    from kvquant_amd import cache, ops
+    from tests import tree_check as tc
+    Hkv, G, L0, S = 2, 4, 60, 7
+    monkeypatch.setattr(ops, "CHUNK_GROUPED", entry != "heads")
+    assert ops.chunk_attention_route(Hkv * G, Hkv, S) == ("heads" if entry == "heads" else "grouped")
+    q = cc.queries(Hkv * G, S, DEV, 13)
+    outs = []
+    for explicit in (False, True):
+        kc, vc, k, v, ks, vs = rc.make(bits, Hkv, L0, S, None, device=DEV, seed=3)
+        rope = (ops.rope_freqs(kc.rope_theta, DEV), 1.0) if explicit else None
+        cache.chunk_kv(kc, vc, q, k, v)                # (packs the chunk into columns L0 .. L0 + S - 1)
+        layer = cache.layer_struct(kc, vc)
+        if entry == "tree":
+            outs.append(ops.chunk_attention_tree(layer, Hkv * G, L0, q, tc.SHAPES["random"](S), rope=rope))
+        else:
+            outs.append(ops.chunk_attention(layer, Hkv * G, L0, q, rope=rope))
+    torch.cuda.synchronize()
+    assert torch.isfinite(outs[0]).all()
+    assert torch.equal(outs[0], outs[1]), (entry, bits)
+
+
 def test_fused_attend_with_table_takes_the_kernel_pair(monkeypatch):
     """KVQ_FUSED_ATTEND=1 (the opt-in fused kernel) with a frequency table: the step takes the kernel pair, whose
     output the explicit theta table reproduces bit for bit"""
