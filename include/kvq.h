@@ -85,6 +85,9 @@ extern "C" {
  *        Later in 403: kvq_chunk_attention_tree[_rope, _workspace_bytes] (draft trees: a tree mask and per-node
  *        positions on the grouped kernel) and kvq_keep_columns (the accepted path moves into contiguous columns).
  *        Additive only, kvq_version() stays 403; the existing chunk kernels are unchanged.
+ *        Later in 403: kvq_chunk_attention_window[_grouped, _workspace_bytes] (sliding-window attention over a ring of
+ *        max_len columns: a column -> token map and a window mask on the chunk kernel).  Additive only, kvq_version()
+ *        stays 403; the existing chunk kernels keep their results bit for bit.
  *        A binding checks `kvq_version() / 100 == KVQ_ABI_MAJOR`. */
 #define KVQ_ABI_MAJOR 4
 KVQ_API int kvq_version(void);
@@ -722,6 +725,42 @@ KVQ_API int kvq_chunk_attention_tree_rope(const kvq_layer *layer, int Hq, int S,
  * cache is refused).  Every violation is KVQ_EINVAL before the launch. */
 KVQ_API int kvq_keep_columns(const kvq_layer *layer, int64_t c0, int S, const uint8_t *keep /* HOST */, int n_keep,
                              void *stream);
+
+/* ---- sliding-window attention over a RING of compressed columns (Mistral-style windows, sinks + recent window) -------
+ * The layer's arrays are a ring of C = layer->max_len columns (C % 64 == 0): compressed token n (0-based; its position is
+ * layer->pos_offset + n) lives in column n mod C.  Keys are cached pre-RoPE and a column's bytes do not depend on its
+ * position, so a ring needs no re-quantisation and no re-rotation -- only kernels that know which token a column holds.
+ * The chunk's S tokens n0 .. n0+S-1 are already packed into columns (n0 + i) mod C when the entry is called; N = n0 + S.
+ *   - the resident columns are c < min(N, C); column c holds token n(c) = c + C * floor((N - 1 - c) / C) and is rotated
+ *     at position layer->pos_offset + n(c);
+ *   - query i (RoPE'd by the caller at layer->pos_offset + n0 + i) attends to the n_sink fp16 sink tokens (always, at
+ *     their own positions) and to column c iff n0 + i - window < n(c) <= n0 + i: `window` keys including its own, the
+ *     mask of transformers' Mistral attention.  With n_sink == 0 this is exactly Mistral's attention, with sinks it is
+ *     sinks + recent window (StreamingLLM).
+ * Everything else -- q / out / sinks layout, G = Hq / layer->H in 1 .. 8, partials, deterministic merge, rope (NULL:
+ * the theta rule) -- as kvq_chunk_attention_rope; the _grouped twin takes G >= 2 and S <= 32 as
+ * kvq_chunk_attention_grouped does.  The split plan counts the tiles of the resident columns; a tile or a split that no
+ * row sees contributes exact zeros / a (-inf, 0) partial that the merge skips.  While N <= C and window >= N the output
+ * equals kvq_chunk_attention[_grouped]_rope's on the same cache bit for bit.
+ * KVQ_EINVAL before any launch, and 0 from the _workspace_bytes functions: window < 1, window + S - 1 > max_len (a token
+ * row 0 still needs would have been overwritten by the chunk), max_len % 64 != 0, n0 < 0, pos_offset + n0 + S >= 2^31
+ * (the workspace functions, which do not see pos_offset: n0 + S >= 2^31) and every shape the plain entries refuse.
+ * The fused packs (kvq_pack_k_fused / kvq_pack_v_fused, the fused appends) write CONTIGUOUS columns: a chunk that
+ * crosses the wrap is packed by the caller as two calls, columns n0 mod C .. C-1 and 0 .. (n0 + S - 1) mod C.  They
+ * overwrite every byte a column owns, so a ring column needs no clearing before it is reused. */
+KVQ_API size_t kvq_chunk_attention_window_workspace_bytes(int Hq, int Hkv, int S, int64_t n0, int64_t window,
+                                                          int64_t max_len);
+KVQ_API int kvq_chunk_attention_window(const kvq_layer *layer, int Hq, int S, int64_t n0, int64_t window, const void *q,
+                                       int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                       const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                       size_t workspace_bytes, const kvq_rope *rope /* NULL = theta rule */, void *stream);
+KVQ_API size_t kvq_chunk_attention_window_grouped_workspace_bytes(int Hq, int Hkv, int S, int64_t n0, int64_t window,
+                                                                  int64_t max_len);
+KVQ_API int kvq_chunk_attention_window_grouped(const kvq_layer *layer, int Hq, int S, int64_t n0, int64_t window,
+                                               const void *q, int64_t q_stride_h, int64_t q_stride_s,
+                                               const uint16_t *k_sink, const uint16_t *v_sink, int n_sink, float *out,
+                                               void *workspace, size_t workspace_bytes,
+                                               const kvq_rope *rope /* NULL = theta rule */, void *stream);
 
 /* ---- uncapped ("orig") Dense-and-Sparse variants, 4 bit only ------------------ */
 

@@ -137,6 +137,11 @@ SIGNATURES = {
     "kvq_chunk_attention_tree": (_i, [_ly, _i, _i, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp]),
     "kvq_chunk_attention_tree_rope": (_i, [_ly, _i, _i, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _sz, _vp, _rp, _vp]),
     "kvq_keep_columns": (_i, [_ly, _i64, _i, _vp, _i, _vp]),
+    "kvq_chunk_attention_window_workspace_bytes": (_sz, [_i, _i, _i, _i64, _i64, _i64]),
+    "kvq_chunk_attention_window": (_i, [_ly, _i, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _sz, _rp, _vp]),
+    "kvq_chunk_attention_window_grouped_workspace_bytes": (_sz, [_i, _i, _i, _i64, _i64, _i64]),
+    "kvq_chunk_attention_window_grouped": (_i, [_ly, _i, _i, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _sz, _rp,
+                                                _vp]),
     "kvq_append_k_sparse_orig": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "kvq_append_v_sparse_orig": (_i, [_vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _i, _i, _i64, _i64, _vp]),
     "kvq_spmv_k_rope_csr": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _f, _i, _vp]),

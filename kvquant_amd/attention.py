@@ -43,6 +43,39 @@ def chunk_route(klen, q_len, sinks, fast):
     return route
 
 
+def window_capacity(window, slack=256):
+    """columns of the ring cache of a sliding-window layer: window + slack rounded up to the 64-column tile.  The slack
+    is what a chunk may add (and a rollback take back) beyond the window: pieces of capacity - window + 1 rows."""
+    W, slack = int(window), int(slack)
+    if W < 1 or slack < 0:
+        raise ValueError("sliding_window must be >= 1 and window_slack >= 0 (got %d, %d)" % (W, slack))
+    return 64 * ((W + slack + 63) // 64)
+
+
+def window_route(klen, q_len, sinks, window, capacity):
+    """How a sliding-window layer feeds q_len tokens into caches holding klen tokens: [(kind, n), ...] in order.
+    "prefill": the first min(q_len, sinks + window) >= 2 tokens of an empty cache through the prefill kernel (inside
+    that piece the window hides nothing); "token": tokens that still fill the fp16 sink cache, one at a time; "chunk":
+    everything else -- a single decode token included -- through chunk_kv on the ring, capacity - window + 1 rows at
+    most per piece."""
+    route, rest = [], int(q_len)
+    if klen == 0:
+        n = min(rest, sinks + window)
+        if n >= 2:
+            route.append(("prefill", n))
+            klen, rest = n, rest - n
+    fill = min(max(sinks - klen, 0), rest)
+    if fill:
+        route.append(("token", fill))
+        rest -= fill
+    step = capacity - window + 1
+    while rest:
+        n = min(rest, step)
+        route.append(("chunk", n))
+        rest -= n
+    return route
+
+
 _DEPTHS = {}      # the last tree's (depth index tensor, positions) per device: every layer of a model asks for the same
 
 
@@ -147,8 +180,16 @@ class KVQuantAttention(nn.Module):
     def __init__(self, hidden_size=4096, num_heads=32, abits=4, include_sparse=True, first_few_fp16=0,
                  maxseqlen=4096, rope_theta=10000.0, sparsity_threshold=0.99, device=None,
                  dtype=torch.float16, bias=False, make_proj=True, use_orig_sparse=False, compact=False,
-                 num_key_value_heads=None, rope_scaling=None, max_position_embeddings=None):
+                 num_key_value_heads=None, rope_scaling=None, max_position_embeddings=None, sliding_window=None,
+                 window_slack=256):
         super().__init__()
+        # sliding_window=W: the caches are RINGS of window_capacity(W, window_slack) columns (cache.QuantK(window=W)) and
+        # every token sees the fp16 sink tokens and the W newest tokens up to its own; maxseqlen then bounds nothing
+        self.sliding_window = None if not sliding_window else int(sliding_window)
+        ring = {}
+        if self.sliding_window is not None:
+            maxseqlen = window_capacity(self.sliding_window, window_slack)
+            ring = dict(window=self.sliding_window)
         # scaled RoPE: rope_scaling = a transformers rope_scaling / rope_parameters dict or a kvquant_amd.rope.RopeSpec
         # (max_position_embeddings: the model's, which dynamic NTK scales from); None = default RoPE (theta rule)
         self.rope = rope_mod.spec_of(rope_theta, rope_scaling, max_position_embeddings)
@@ -179,11 +220,12 @@ class KVQuantAttention(nn.Module):
         self.kcache = QuantK(bits=abits, hidden_size=kv_hidden, num_heads=self.num_key_value_heads,
                              max_position_embeddings=maxseqlen, include_sparse=include_sparse,
                              sparsity_threshold=sparsity_threshold, rope_theta=rope_theta,
-                             first_few_fp16=first_few_fp16, device=device, compact=compact, rope_scaling=self.rope)
+                             first_few_fp16=first_few_fp16, device=device, compact=compact, rope_scaling=self.rope,
+                             **ring)
         self.vcache = QuantV(bits=abits, hidden_size=kv_hidden, num_heads=self.num_key_value_heads,
                              max_position_embeddings=maxseqlen, include_sparse=include_sparse,
                              sparsity_threshold=sparsity_threshold, first_few_fp16=first_few_fp16,
-                             device=device, compact=compact)
+                             device=device, compact=compact, **ring)
         if first_few_fp16 > 0:
             self.kcache_fp16 = torch.zeros((1, self.num_key_value_heads, self.head_dim, first_few_fp16), dtype=dtype,
                                            device=self.kcache.device)
@@ -223,6 +265,8 @@ class KVQuantAttention(nn.Module):
         accepted root-to-leaf path) in both caches, one launch (cache.keep_kv -> kvq_keep_columns); the lengths move back
         by S - len(keep).  keep = 0 .. n-1 is rollback(S - n).  Refused like rollback, and for compact caches."""
         kc = self.kcache
+        if self.sliding_window is not None:
+            raise ValueError("keep_path: draft trees are not taken on a sliding-window layer (ring caches)")
         if kc.klen < self.first_few_fp16:
             raise ValueError("keep_path while the fp16 sink cache is still filling (len %d < %d)"
                              % (kc.klen, self.first_few_fp16))
@@ -240,6 +284,13 @@ class KVQuantAttention(nn.Module):
         activation dtype.  Returns attn_output [1, q_len, hidden] (before o_proj).  Grouped-query attention
         (G = num_kv_groups > 1) runs the same three phases -- prefill, sink filling with the KV heads repeated per
         group, one-call decode -- and refuses the configurations for which MHA falls back to the multi-launch tail."""
+        if self.sliding_window is not None:
+            return self._attend_window(query_states, key_states, value_states)
+        return self._attend_linear(query_states, key_states, value_states)
+
+    def _attend_linear(self, query_states, key_states, value_states):
+        """attend() over linear caches: prefill, sink filling, decode, chunks.  A sliding-window layer runs the prefill
+        piece and the sink-filling tokens of its route through it (_attend_window); neither touches a ring's wrap."""
         bsz, H, q_len, hd = query_states.shape
         assert bsz == 1, "batch 1 only (ML:1801)"
         if self.tree is not None and not (q_len > 1 and self.kcache.klen > 0):
@@ -334,6 +385,33 @@ class KVQuantAttention(nn.Module):
         if sinks > 0:
             out = out + torch.matmul(sink_probs.view(1, H, 1, sinks), self.vcache_fp16)
         return out.transpose(1, 2).contiguous().reshape(bsz, q_len, self.hidden_size)
+
+    # ------------------------------------------------------------------ sliding-window layers (ring caches)
+    def _attend_window(self, query_states, key_states, value_states):
+        """attend() of a sliding-window layer (window_route): the existing prefill and sink filling for the start of
+        the stream, everything else -- decode tokens, follow-up chunks, the rest of a long prompt, chain drafts --
+        through _attend_chunk on the ring caches."""
+        if self.tree is not None:
+            raise ValueError("draft trees are not taken on a sliding-window layer (ring caches)")
+        if not (query_states.dtype == torch.float16 and self.head_dim == 128
+                and (self.first_few_fp16 == 0 or self.kcache_fp16.dtype == torch.float16)):
+            raise ValueError("sliding-window attention runs the chunk kernel only: fp16 activations, fp16 sink caches, "
+                             "head_dim 128")
+        q_len = query_states.shape[2]
+        route = window_route(self.kcache.klen, q_len, self.first_few_fp16, self.sliding_window, self.kcache.max_len)
+        outs, i = [], 0
+        for kind, n in route:
+            q, k, v = (t[:, :, i:i + n] for t in (query_states, key_states, value_states))
+            if kind == "chunk":
+                outs.append(self._attend_chunk(q, k, v))
+            elif kind == "prefill":
+                outs.append(self._attend_linear(q, k, v))
+            else:
+                outs.extend(self._attend_linear(q[:, :, j:j + 1], k[:, :, j:j + 1], v[:, :, j:j + 1]) for j in range(n))
+            i += n
+        if len(outs) == 1:
+            return outs[0]
+        return torch.cat([o.to(query_states.dtype) for o in outs], dim=1)
 
     # ------------------------------------------------------------------ q_len > 1 on a warm cache
     def chunk_fast(self, query_states):

@@ -69,6 +69,68 @@ def _keep_columns(length, sinks, S, keep):
     return c0, len(keep)
 
 
+# ---- ring caches (window=W): compressed token n lives in column n mod C, C = max_position_embeddings ------------------
+def ring_token(c, N, C):
+    """the token column c of a ring of C columns holds once N tokens have been taken (c < min(N, C))"""
+    return c + C * ((N - 1 - c) // C)
+
+
+def ring_pieces(n0, S, C):
+    """[(column, offset, count), ...]: tokens n0 .. n0+S-1 in the contiguous column runs the fused packs write --
+    one piece, or two where the chunk crosses the wrap.  ValueError for more tokens than the ring has columns."""
+    n0, S, C = int(n0), int(S), int(C)
+    if S > C:
+        raise ValueError("a ring of %d columns cannot take %d tokens in one pack" % (C, S))
+    col = n0 % C
+    first = min(S, C - col)
+    pieces = [(col, 0, first)] if first else []
+    if S > first:
+        pieces.append((0, first, S - first))
+    return pieces
+
+
+def ring_check(window, C, what="window"):
+    """the window of a ring cache of C columns as an int; ValueError unless 1 <= window <= C and C % 64 == 0"""
+    W, C = int(window), int(C)
+    if W < 1 or C < 1 or C % 64 or W > C:
+        raise ValueError("%s = %d on a ring of %d columns: 1 <= window <= capacity, capacity a multiple of 64" % (what, W, C))
+    return W
+
+
+def ring_truncate_ok(N, n, window, C, high_water):
+    """may a ring that holds N tokens (most ever: high_water) drop its newest n?  False if the token after the rollback
+    would need a token the ring has already overwritten"""
+    return not (high_water > C and (N - n) - window + 1 < high_water - C)
+
+
+def _ring_refuse(cache, what):
+    if getattr(cache, "window", None) is not None:
+        raise ValueError("%s: this is a ring cache (window=%d) -- ring caches are attended through chunk_kv"
+                         % (what, cache.window))
+
+
+def _ring_init(cache, window, compact, use_orig_sparse, include_sparse):
+    """window= of QuantK / QuantV: None (a linear cache), or the sliding window of a ring whose capacity is
+    max_position_embeddings"""
+    cache.window = None
+    cache.high_water = 0       # most compressed tokens ever held since reset()
+    if window is None:
+        return
+    if compact or use_orig_sparse or not include_sparse:
+        raise ValueError("window= needs an include_sparse cache in the reference outlier format (not compact, not "
+                         "use_orig_sparse): a ring has no token-by-token route")
+    cache.window = ring_check(window, cache.max_len)
+
+
+def _ring_truncate(cache, length, n_tokens):
+    """column slices (up to two) that truncate(n_tokens) zeroes on a ring cache of `length` tokens, after the checks"""
+    lo, hi = _truncate_columns(length, cache.first_few_fp16, n_tokens)
+    if not ring_truncate_ok(hi, hi - lo, cache.window, cache.max_len, cache.high_water):
+        raise ValueError("truncate(%d): the token after the rollback would need tokens this ring of %d columns has "
+                         "overwritten (window %d, %d tokens taken)" % (n_tokens, cache.max_len, cache.window, cache.high_water))
+    return [slice(c, c + n) for c, _, n in ring_pieces(lo, hi - lo, cache.max_len)], hi - lo
+
+
 def _default_device(device):
     if device is not None:
         return torch.device(device)
@@ -82,7 +144,7 @@ class QuantK(nn.Module):
 
     def __init__(self, bits=2, hidden_size=4096, num_heads=32, max_position_embeddings=-1,
                  include_sparse=False, sparsity_threshold=0.99, rope_theta=10000, use_orig_sparse=False,
-                 first_few_fp16=0, device=None, compact=False, outlier_width=None, rope_scaling=None):
+                 first_few_fp16=0, device=None, compact=False, outlier_width=None, rope_scaling=None, window=None):
         super().__init__()
         if bits not in (2, 3, 4):
             raise ValueError("bits must be 2, 3 or 4")
@@ -110,6 +172,9 @@ class QuantK(nn.Module):
         self.outlier_threshold_lower = None
         self.max_len = max_position_embeddings
         self.klen = 0
+        # window=W: a RING of max_position_embeddings columns for sliding-window attention (token n in column n mod C);
+        # klen keeps counting every token ever taken
+        _ring_init(self, window, compact, use_orig_sparse, include_sparse)
         dev = _default_device(device)
         self.kcache = torch.zeros((num_heads, (self.head_dim // 32) * bits, self.max_len), dtype=torch.int32,
                                   device=dev)
@@ -192,6 +257,7 @@ class QuantK(nn.Module):
     def reset(self):
         """ML:416-434 (plain zero fill instead of a masked assignment)."""
         self.klen = 0
+        self.high_water = 0
         self.kcache.zero_()
         if self.include_sparse:
             for t in (self.outliers, self.outlier_indices, self.outliers_t, self.outlier_indices_t):
@@ -206,16 +272,22 @@ class QuantK(nn.Module):
         tokens (which count in klen) or below zero."""
         if self.use_orig_sparse:
             raise NotImplementedError("truncate: the uncapped (orig) CSR state grows by concatenation")
-        lo, hi = _truncate_columns(self.klen, self.first_few_fp16, n_tokens)
-        self.kcache[:, :, lo:hi] = 0
-        if self.include_sparse:
-            for t in (self.outliers, self.outlier_indices):
-                if t is not None:
-                    t[lo:hi] = 0
-            for t in (self.outliers_t, self.outlier_indices_t):
-                if t is not None:
-                    t[:, lo:hi] = 0
-        self.klen -= hi - lo
+        if self.window is not None:
+            # (a ring: the dropped tokens' columns, in up to two slices; ValueError past the slack)
+            cols, n = _ring_truncate(self, self.klen, n_tokens)
+        else:
+            lo, hi = _truncate_columns(self.klen, self.first_few_fp16, n_tokens)
+            cols, n = [slice(lo, hi)], hi - lo
+        for sl in cols:
+            self.kcache[:, :, sl] = 0
+            if self.include_sparse:
+                for t in (self.outliers, self.outlier_indices):
+                    if t is not None:
+                        t[sl] = 0
+                for t in (self.outliers_t, self.outlier_indices_t):
+                    if t is not None:
+                        t[:, sl] = 0
+        self.klen -= n
 
     def keep_columns(self, S, keep):
         """Of the newest S <= 32 compressed tokens (the nodes of a verified draft tree, packed in row order) keep the
@@ -228,6 +300,8 @@ class QuantK(nn.Module):
             raise NotImplementedError("keep_columns: the uncapped (orig) CSR state grows by concatenation")
         if self.compact:
             raise ValueError("keep_columns moves the reference outlier format; compact caches are not taken")
+        if self.window is not None:
+            raise ValueError("keep_columns: draft trees are not taken on a ring cache (window=%d)" % self.window)
         c0, n = _keep_columns(self.klen, self.first_few_fp16, S, keep)
         layer, alive = ops.side_layer(kc=self)
         ops.keep_columns(layer, c0, S, keep, self.device)
@@ -294,6 +368,7 @@ class QuantK(nn.Module):
         scores f32 [q_len, H, L] (one launch).  No host synchronisation."""
         if self.compact:
             raise NotImplementedError("compact caches are read by decode_kv only (the reference-format kernels need the rows)")
+        _ring_refuse(self, "append_and_score")
         pos = self.klen - self.first_few_fp16
         rope = self.rope_table(self.klen + 1)
         if self.include_sparse:
@@ -334,6 +409,18 @@ class QuantK(nn.Module):
         col0 = _pack_col0(self.klen, self.first_few_fp16)
         if self.compact and not fused:
             raise NotImplementedError("compact caches take the fused prefill pack only")
+        if self.window is not None:
+            # a ring: token n at column n mod C, in two pieces across the wrap (the fused pack writes contiguous columns)
+            if not fused:
+                raise ValueError("parallel_pack(fused=False): ring caches take the fused pack only")
+            for c, s0, n in ring_pieces(col0, S, self.max_len):
+                ops.pack_k_fused(self.bits, self.kcache, self.lookup_table, self.offset_table(), k[..., s0:s0 + n].contiguous(),
+                                 self.outlier_threshold_lower, self.outlier_threshold_upper, self.outliers,
+                                 self.outlier_indices, self.num_outliers // 2, c, self.outliers_t,
+                                 self.outlier_indices_t)
+            self.klen += S
+            self.high_water = max(self.high_water, col0 + S)
+            return
         if fused:
             # one launch: pack + exact top-k selection + outlier rows (+ mirror), one workgroup per token
             ops.pack_k_fused(self.bits, self.kcache, self.lookup_table, self.offset_table(), k,
@@ -359,6 +446,7 @@ class QuantK(nn.Module):
         """ML:504-559: outliers = everything outside the thresholds (code 7, residual x - zeropoint) kept
         in a growing CSR matrix; dense scores + CSR SpMV."""
         assert self.include_sparse and self.bits == 4
+        _ring_refuse(self, "forward_fused_sparse_orig")
         from . import quant_cuda as qc
         k = k.flatten().float().contiguous()
         q = q.float().transpose(0, 1).contiguous()
@@ -416,7 +504,7 @@ class QuantV(nn.Module):
 
     def __init__(self, bits=2, hidden_size=4096, num_heads=32, max_position_embeddings=-1,
                  include_sparse=False, sparsity_threshold=0.99, first_few_fp16=0, device=None, compact=False,
-                 outlier_width=None):
+                 outlier_width=None, window=None):
         super().__init__()
         if bits not in (2, 3, 4):
             raise ValueError("bits must be 2, 3 or 4")
@@ -432,6 +520,7 @@ class QuantV(nn.Module):
         self.sparsity_threshold = sparsity_threshold
         self.include_sparse = include_sparse
         self.max_len = max_position_embeddings
+        _ring_init(self, window, compact, False, include_sparse)      # (window=W: a ring, see QuantK)
         dev = _default_device(device)
         self.lookup_table = torch.zeros((self.max_len, 2 ** bits), dtype=torch.float32, device=dev)
         self.vcache = torch.zeros((num_heads, (self.head_dim // 32) * bits, self.max_len), dtype=torch.int32,
@@ -465,6 +554,7 @@ class QuantV(nn.Module):
     def reset(self):
         """ML:1028-1042."""
         self.vlen = 0
+        self.high_water = 0
         self.lookup_table.zero_()
         self.vcache.zero_()
         if self.include_sparse:
@@ -477,22 +567,29 @@ class QuantV(nn.Module):
     def truncate(self, n_tokens):
         """Drop the newest n_tokens compressed tokens (QuantK.truncate): vlen moves back; packed words, codebook rows
         (both tables) and outlier rows of the dropped columns are zero again, as reset() leaves them."""
-        lo, hi = _truncate_columns(self.vlen, self.first_few_fp16, n_tokens)
-        self.vcache[:, :, lo:hi] = 0
-        self.lookup_table[lo:hi] = 0
-        if self.lookup_table2 is not None:
-            self.lookup_table2[lo:hi] = 0
-        if self.include_sparse:
-            if self.outliers is not None:
-                self.outliers[lo:hi] = 0
-            self.outlier_indices[lo:hi] = 0
-        self.vlen -= hi - lo
+        if self.window is not None:
+            cols, n = _ring_truncate(self, self.vlen, n_tokens)
+        else:
+            lo, hi = _truncate_columns(self.vlen, self.first_few_fp16, n_tokens)
+            cols, n = [slice(lo, hi)], hi - lo
+        for sl in cols:
+            self.vcache[:, :, sl] = 0
+            self.lookup_table[sl] = 0
+            if self.lookup_table2 is not None:
+                self.lookup_table2[sl] = 0
+            if self.include_sparse:
+                if self.outliers is not None:
+                    self.outliers[sl] = 0
+                self.outlier_indices[sl] = 0
+        self.vlen -= n
 
     def keep_columns(self, S, keep):
         """QuantK.keep_columns for the value cache: packed words, codebook rows (both tables) and outlier rows of the kept
         tokens move to the front of the chunk's columns, the rest is zero again; vlen moves back by S - len(keep)."""
         if self.compact:
             raise ValueError("keep_columns moves the reference outlier format; compact caches are not taken")
+        if self.window is not None:
+            raise ValueError("keep_columns: draft trees are not taken on a ring cache (window=%d)" % self.window)
         c0, n = _keep_columns(self.vlen, self.first_few_fp16, S, keep)
         layer, alive = ops.side_layer(vc=self)
         ops.keep_columns(layer, c0, S, keep, self.device)
@@ -547,6 +644,7 @@ class QuantV(nn.Module):
         """The GPU-resident core of forward_fused_sparse: p f32 [q_len, H, L+1] probabilities,
         v f32 [C].  Appends v (thresholds, codebook row(s), pack, outlier row: one launch) and returns
         f32 [q_len, H, hd] (two launches).  No host synchronisation.  include_sparse only."""
+        _ring_refuse(self, "append_and_mix")
         pos = self.vlen - self.first_few_fp16
         ops.append_v_fused(self.bits, self.vcache, self.lookup_table, self.lut, v, self.outliers,
                            self.outlier_indices, self.num_outliers // 2, pos, self.vnorm_args())
@@ -565,6 +663,7 @@ class QuantV(nn.Module):
         happens inside the fused GPU append."""
         if self.compact:
             raise NotImplementedError("compact caches are read by decode_kv only")
+        _ring_refuse(self, "forward_fused_sparse")
         score = score.float()
         v_in = v.flatten()
         v = v_in.float().contiguous()
@@ -636,6 +735,16 @@ class QuantV(nn.Module):
         col0 = _pack_col0(self.vlen, self.first_few_fp16)
         if self.compact and upper_outlier_vals is not None:
             raise NotImplementedError("compact caches take the fused prefill pack only")
+        if self.window is not None:
+            if upper_outlier_vals is not None:
+                raise ValueError("parallel_pack with top-k tensors: ring caches take the fused pack only")
+            for c, s0, n in ring_pieces(col0, S, self.max_len):
+                ops.pack_v_fused(self.bits, self.vcache, self.lookup_table, self.lut, v[..., s0:s0 + n].contiguous(),
+                                 self.outliers, self.outlier_indices, self.num_outliers // 2, c,
+                                 self.vnorm_args(prefill=True))
+            self.vlen += S
+            self.high_water = max(self.high_water, col0 + S)
+            return
         if upper_outlier_vals is None:
             # one launch: top-(k+1) selection, per-token codebook rows, pack, outlier rows
             ops.pack_v_fused(self.bits, self.vcache, self.lookup_table, self.lut, v, self.outliers,
@@ -732,6 +841,8 @@ def decode_kv(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     1987-1995; five small launches per layer otherwise).
     Returns (out f32 [1, H, hd], sink_probs f16 [H, n_sink] or None).  Sparse (include_sparse) caches only.
     Grouped-query attention: q of Hq = G * H rows (1 < G <= 8) over caches of H KV heads takes decode_kv_gqa."""
+    _ring_refuse(kc, "decode_kv")
+    _ring_refuse(vc, "decode_kv")
     if q.dim() == 2 and q.shape[0] != kc.num_heads:
         return decode_kv_gqa(kc, vc, q, k, v, sink_scores, k_sink, v_sink)
     if not (kc.include_sparse and vc.include_sparse):
@@ -792,6 +903,8 @@ def decode_kv_gqa(kc, vc, q, k, v, sink_scores=None, k_sink=None, v_sink=None):
     (f16 [Hkv, 128, n_sink], post-RoPE) / v_sink (f16 [Hkv, n_sink, 128]), the fp16 sink caches of the KV heads: their
     scores and values are repeated per group here (torch glue over the few sink tokens).
     Returns (out f32 [1, Hq, hd], sink_probs f16 [Hq, n_sink] or None)."""
+    _ring_refuse(kc, "decode_kv")
+    _ring_refuse(vc, "decode_kv")
     H = kc.num_heads
     Hq = int(q.shape[0])
     if Hq % H or not 1 <= Hq // H <= 8:
@@ -838,6 +951,8 @@ def keep_kv(kc, vc, S, keep):
         raise ValueError("keep_columns moves Dense-and-Sparse caches in the reference outlier format (not compact)")
     if kc.klen != vc.vlen:
         raise ValueError("keep_columns: K and V caches are out of step (%d / %d tokens)" % (kc.klen, vc.vlen))
+    if getattr(kc, "window", None) is not None or getattr(vc, "window", None) is not None:
+        raise ValueError("keep_columns: draft trees are not taken on a ring cache")
     c0, n = _keep_columns(kc.klen, kc.first_few_fp16, S, keep)
     ops.keep_columns(layer_struct(kc, vc), c0, S, keep, kc.device)
     kc.klen -= int(S) - n
@@ -856,6 +971,10 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None, parent=None):
     parent[i] < i (parent[0] ignored).  The packs are the same (a column's bytes do not depend on its position); the
     attention is kvq_chunk_attention_tree: query i (RoPE'd by the caller at klen + depth[i]) sees the cache, itself and
     its ancestors, and column c0 + j rotates at the position of its depth.  keep_kv() then keeps the accepted path.
+    Ring caches (QuantK / QuantV(window=W), S >= 1): the chunk is packed at columns (c0 + i) mod C and attended with
+    kvq_chunk_attention_window -- query i sees the sink tokens and the W newest tokens up to its own, each column rotated
+    at the position of the token it holds.  ValueError unless W + S - 1 <= C (feed a longer chunk in pieces), and for
+    a tree.
     Returns f32 [S, Hq, 128].  Dense-and-Sparse caches in the reference outlier format (not compact) only."""
     if not (kc.include_sparse and vc.include_sparse):
         raise ValueError("chunk_kv needs include_sparse caches")
@@ -871,6 +990,33 @@ def chunk_kv(kc, vc, q, k, v, k_sink=None, v_sink=None, parent=None):
     if Hq % kc.num_heads or not 1 <= Hq // kc.num_heads <= 8:
         raise ValueError("chunk_kv: q has %d heads, the caches %d KV heads (Hq = G * Hkv, 1 <= G <= 8)" % (Hq, kc.num_heads))
     c0 = kc.klen - sinks
+    W = getattr(kc, "window", None)
+    if W != getattr(vc, "window", None):
+        raise ValueError("chunk_kv: K and V caches differ in their window (%r / %r)" % (W, getattr(vc, "window", None)))
+    if W is not None:
+        # ring caches (S >= 1): token n in column n mod C; a row must still find the W - 1 tokens before it
+        if parent is not None:
+            raise ValueError("chunk_kv: draft trees are not taken on a ring cache (window=%d)" % W)
+        if kc.max_len != vc.max_len or W + S - 1 > kc.max_len:
+            raise ValueError("chunk_kv: a chunk of %d tokens under a window of %d needs a ring of %d columns, this one "
+                             "has %d -- feed at most %d tokens at a time" % (S, W, W + S - 1, kc.max_len, kc.max_len - W + 1))
+        rope = kc.rope_table(kc.klen + S)
+        layer = layer_struct(kc, vc)
+        ks = None if sinks == 0 else k_sink.contiguous()
+        vs = None if sinks == 0 else v_sink.contiguous()
+        # everything the window call would refuse is refused here, before the pack moves klen / vlen
+        routes = [ops.chunk_attention_window_check(layer, Hq, c0 + s0, W, q[:, s0:s0 + CHUNK_PIECE], ks, vs, rope)
+                  for s0 in range(0, S, CHUNK_PIECE)]
+        kc.parallel_pack(k)
+        vc.parallel_pack(v)
+        out = torch.empty((S, Hq, kc.head_dim), dtype=torch.float32, device=kc.device)
+        # (a later piece is the same call with n0 moved on: the columns the chunk's later tokens have overwritten held
+        #  tokens <= n0 - W, which no row of the chunk sees)
+        for s0 in range(0, S, CHUNK_PIECE):
+            n = min(CHUNK_PIECE, S - s0)
+            ops.chunk_attention_window(layer, Hq, c0 + s0, W, q[:, s0:s0 + n], out[s0:s0 + n], ks, vs, rope=rope,
+                                       grouped=routes[s0 // CHUNK_PIECE])
+        return out
     if c0 + S > kc.max_len:
         raise ValueError("chunk_kv: %d + %d tokens exceed the cache (%d columns)" % (c0, S, kc.max_len))
     if parent is not None:
@@ -921,6 +1067,8 @@ def shard_attention(kc, vc, q, k=None, v=None, pos_base=0, record=None, k_sink=N
     (no cached tokens, no new one, no sinks) returns zeros with (M, Z) = (-inf, 0).  Sparse caches with the outlier mirror."""
     if not (kc.include_sparse and vc.include_sparse):
         raise ValueError("shard_attention needs include_sparse caches")
+    _ring_refuse(kc, "shard_attention")
+    _ring_refuse(vc, "shard_attention")
     rope_mod.require_default(getattr(kc, "rope", None), "shard_attention (the token-sharded path)")
     if q.dim() != 2 or q.shape[0] != kc.num_heads:
         raise ValueError("shard_attention: q must be [%d, 128] -- the token-sharded path is MHA only (no grouped-query "

@@ -34,6 +34,16 @@
 // position of its DEPTH, pos_offset + c0 + depth[j], so siblings share a position.  anc / depth ride in the kernel
 // arguments (Args::tree).  A chain (parent[i] = i - 1) is the grouped kernel, bit for bit.
 //
+// Window variant (WN, kvq_chunk_attention_window[_grouped]: sliding-window attention over a RING of C = max_len columns,
+// per-head and grouped geometries): compressed token n lives in column n mod C, the chunk's tokens n0 .. n0+S-1 are
+// already packed, N = n0 + S.  The resident columns are c < min(N, C); column c holds token
+// n(c) = c + C * floor((N - 1 - c) / C) = c + base - (c > r ? C : 0), base = C * ((N - 1) / C), r = (N - 1) % C (host),
+// and rotates at pos_offset + n(c).  Row i sees the sinks and column c iff n0 + i - W < n(c) <= n0 + i.  A ring tile may
+// be masked in part anywhere: a wave takes the mask on every tile that is not visible in full to all of its rows and
+// skips one that none of them sees (a masked tile that is not skipped adds exact zeros to the running sums); every
+// workgroup decodes all resident tiles of its split.  The split plan counts the resident tiles, partials and merge are
+// unchanged.  With N <= C and W >= N the statements reduce to the plain kernel's, bit for bit.
+//
 // kvq_keep_columns (end of the file): after a tree round the accepted root-to-leaf path moves into contiguous columns
 // -- a copy of packed words, codebook rows and outlier rows; the keys are stored pre-RoPE, nothing is re-rotated.
 #include "kvq_common.h"
@@ -80,13 +90,18 @@ struct Args {
   const float *rt_freq;              // RT (scaled RoPE, kvq.h: kvq_rope): the K tiles rotate with the frequencies rt_freq
   float rt_af;                       // [64] and (cos, sin) scaled by rt_af (before the fp16 rounding of the tile)
   Tree tree;                         // TR only (kernel arguments a variant does not read are never loaded)
+  // WN only (c0 is then n0, the chunk's first TOKEN): the window, the ring's capacity, its resident columns
+  // min(N, C), and the column -> token map n(c) = c + wn_base - (c > wn_r ? wn_cap : 0); all below 2^31
+  int wn_window, wn_cap, wn_res, wn_r, wn_base;
 };
 
 // One kernel for the per-head (GR = TR = false), grouped (GR) and tree (GR and TR) geometries.  TR: tree mask and per-node
-// positions from LDS copies of a.tree (the barriers in front of the first use order them).
-template <int BITS, bool RT, bool GR, bool TR>
+// positions from LDS copies of a.tree (the barriers in front of the first use order them).  WN: the window / ring variant
+// of the per-head and grouped geometries.
+template <int BITS, bool RT, bool GR, bool TR, bool WN = false>
 __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
   static_assert(!TR || GR, "the tree variant runs in the grouped geometry");
+  static_assert(!(TR && WN), "no draft trees on a ring");
   constexpr int N = 1 << BITS;
   constexpr int WPH = kD / 32 * BITS;
   __shared__ float klut[kD * N];
@@ -126,9 +141,9 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
   const int qrow = q0 + ql;
   const int qrc = qrow < a.S ? qrow : a.S - 1;
   const int64_t ml = a.max_len;
-  const int64_t Lc = a.c0 + a.S;                       // compressed columns after the append
+  const int64_t Lc = WN ? (int64_t)a.wn_res : a.c0 + a.S;   // compressed columns after the append (WN: resident ones)
   const int rows_end = (q0w + kQW < a.S) ? q0w + kQW : a.S;
-  const int64_t kend = a.c0 + rows_end;                // columns [0, kend) matter to this workgroup
+  const int64_t kend = WN ? Lc : a.c0 + rows_end;      // columns [0, kend) matter to this workgroup
   const int n_tiles = (int)((kend + kKV - 1) / kKV);
   const int t_beg = split * a.tps;
   const int t_end = (t_beg + a.tps < n_tiles) ? t_beg + a.tps : n_tiles;
@@ -145,10 +160,28 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
 
   // ---- S^T, mask, online softmax, O^T of one staged tile.  sink: key j of the tile is sink token j (no causal mask);
   // else key j is compressed column t0 + j, visible to row q iff t0 + j <= c0 + q (and < Lc); TR: iff t0 + j < c0 or
-  // node t0 + j - c0 is in the row's ancestor set (which has no bit at or above S)
+  // node t0 + j - c0 is in the row's ancestor set (which has no bit at or above S); WN: iff the column's token n(c) is
+  // in (c0 + q - W, c0 + q]
   auto attend_tile = [&](bool sink, int64_t t0) __attribute__((always_inline)) {
-    if (!(has_rows && q0 < a.S && (sink || t0 <= a.c0 + q0 + kQB - 1))) return;
-    const bool diag = sink ? a.n_sink < kKV : TR ? t0 + kKV > a.c0 : (t0 + kKV - 1 > a.c0 + q0 || t0 + kKV > Lc);
+    if (!(has_rows && q0 < a.S && (sink || WN || t0 <= a.c0 + q0 + kQB - 1))) return;
+    bool diag = sink ? a.n_sink < kKV
+                : TR ? t0 + kKV > a.c0
+                     : (t0 + kKV - 1 > a.c0 + q0 || t0 + kKV > Lc);
+    if constexpr (WN) {
+      if (!sink) {
+        // the tile's tokens are contiguous unless it holds the ring's newest column wn_r: then the wave skips a tile
+        // none of its rows sees and takes one all of them see in full without the mask, as the plain kernel does
+        const int c_lo = (int)t0, c_hi = (int)t0 + kKV - 1;
+        const int q_lo = (int)a.c0 + q0, q_hi = (int)a.c0 + (q0 + kQB - 1 < a.S ? q0 + kQB - 1 : a.S - 1);
+        diag = true;
+        if (c_hi <= a.wn_r || c_lo > a.wn_r) {
+          const int off = c_lo > a.wn_r ? a.wn_base - a.wn_cap : a.wn_base;
+          const int t_lo = c_lo + off, t_hi = c_hi + off;
+          if (t_lo > q_hi || t_hi <= q_lo - a.wn_window) return;
+          diag = !(t_hi <= q_lo && t_lo > q_hi - a.wn_window && c_hi < a.wn_res);
+        }
+      }
+    }
     // TR: bit j of vism[kb] = key kb * 32 + 4 * hi + j of the tile is visible to this lane's row (rows >= S: no node)
     uint32_t vism[2] = {0u, 0u};
     if constexpr (TR) {
@@ -164,8 +197,16 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
               [&](int kb, int r) __attribute__((always_inline)) -> bool {
                 const int j = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 if (sink) return j < a.n_sink;
-                if constexpr (TR) return (vism[kb] >> ((r & 3) + 8 * (r >> 2))) & 1u;
-                else return t0 + j <= a.c0 + qrow && t0 + j < Lc;
+                if constexpr (TR) {
+                  return (vism[kb] >> ((r & 3) + 8 * (r >> 2))) & 1u;
+                } else if constexpr (WN) {
+                  const int c = (int)t0 + j;
+                  const int tok = c + (c > a.wn_r ? a.wn_base - a.wn_cap : a.wn_base);
+                  const int qt = (int)a.c0 + qrc;      // (rows >= S are clamped duplicates that are never written)
+                  return tok <= qt && tok > qt - a.wn_window && c < a.wn_res;
+                } else {
+                  return t0 + j <= a.c0 + qrow && t0 + j < Lc;
+                }
               });
   };
 
@@ -246,6 +287,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(Args a) {
         const int node = (int)(colc - a.c0);           // <= S - 1 (colc < Lc)
         if (node >= 0) pos = (int)a.c0 + tdepth[node];
       }
+      if constexpr (WN) pos += pos > a.wn_r ? a.wn_base - a.wn_cap : a.wn_base;      // the token the column holds
       const float posf = (float)(pos + a.pos_offset);
       const float *kr = kst + skey * kSR;
       float lo[16], hv[16];
@@ -331,14 +373,16 @@ static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // grouped: the plan of the grouped kernel (G >= 2, S <= 32): Hkv workgroup rows in place of Hq x nqb
 // tree (with grouped): the tree variant also takes G = 1, and a tree has at least one draft node (S >= 2)
-static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = false, bool tree = false) {
+// cols >= 0 (the window variant): the tiles are counted over cols resident columns instead of c0 + S
+static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = false, bool tree = false,
+                 int64_t cols = -1) {
   if (Hq <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv > 8 || (int64_t)Hkv * kD > 8192 || S <= 0 || S > kMaxS || c0 < 0 ||
       c0 + S >= (int64_t(1) << 31))
     return false;
   if (grouped && ((Hq / Hkv < 2 && !tree) || S > kQB)) return false;
   if (tree && S < 2) return false;
   p.nqb = (S + kQW - 1) / kQW;
-  const int64_t tiles = (c0 + S + kKV - 1) / kKV;
+  const int64_t tiles = ((cols >= 0 ? cols : c0 + S) + kKV - 1) / kKV;
   const int64_t base = grouped ? (int64_t)Hkv : (int64_t)Hq * p.nqb;
   int64_t ns = (kTargetWorkgroups + base - 1) / base;
   const int64_t cap = tiles / kMinTilesPerSplit > 1 ? tiles / kMinTilesPerSplit : 1;
@@ -352,6 +396,16 @@ static bool plan(int Hq, int Hkv, int S, int64_t c0, Plan &p, bool grouped = fal
   p.o_bytes = align256((size_t)Hq * p.nsplit * S * kD * 4);
   p.ml_bytes = align256((size_t)Hq * p.nsplit * S * 8);
   return true;
+}
+
+// the window variant's plan over a ring of max_len columns (kvq.h: kvq_chunk_attention_window): false for what the plain
+// plan refuses and for window < 1, window + S - 1 > max_len, max_len % 64 != 0
+static bool plan_window(int Hq, int Hkv, int S, int64_t n0, int64_t window, int64_t max_len, Plan &p, bool grouped) {
+  if (window < 1 || max_len <= 0 || max_len % kKV || max_len >= (int64_t(1) << 31) || S <= 0 || n0 < 0 ||
+      window + S - 1 > max_len)
+    return false;
+  const int64_t N = n0 + S;
+  return plan(Hq, Hkv, S, n0, p, grouped, false, N < max_len ? N : max_len);
 }
 
 }  // namespace chunk
@@ -379,18 +433,23 @@ static bool tree_of(const uint8_t *parent, int S, chunk::Tree &t) {
 
 // grouped: the grouped kernel (one workgroup per KV head and split), which plan() takes for G >= 2 and S <= 32 only
 // parent (with grouped; HOST array of S entries): the tree variant, G >= 1 and 2 <= S <= 32
+// window >= 1 (no parent): the window / ring variant, c0 is then n0 (0: the plain kernels)
 static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0, const void *q, int64_t q_stride_h,
                                   int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink, int n_sink,
                                   float *out, void *workspace, size_t workspace_bytes, const kvq_rope *rope, void *stream,
-                                  bool grouped, const uint8_t *parent = nullptr) {
+                                  bool grouped, const uint8_t *parent = nullptr, int64_t window = 0) {
   if (!ly || !q || !out || !rope_ok(rope)) return KVQ_EINVAL;
+  const bool ring = window != 0;
+  if (ring && parent) return KVQ_EINVAL;
   chunk::Args a = {};
   if (parent && !(grouped && tree_of(parent, S, a.tree))) return KVQ_EINVAL;
   const int bits = ly->bits;
   if ((bits != 2 && bits != 3 && bits != 4) || ly->hd != chunk::kD || ly->thr_k <= 0) return KVQ_EINVAL;
   chunk::Plan p;
-  if (!chunk::plan(Hq, ly->H, S, c0, p, grouped, parent != nullptr)) return KVQ_EINVAL;
-  if (ly->max_len <= 0 || ly->max_len >= (int64_t(1) << 31) || c0 + S > ly->max_len || ly->pos_offset < 0 ||
+  if (ring ? !chunk::plan_window(Hq, ly->H, S, c0, window, ly->max_len, p, grouped)
+           : !chunk::plan(Hq, ly->H, S, c0, p, grouped, parent != nullptr))
+    return KVQ_EINVAL;
+  if (ly->max_len <= 0 || ly->max_len >= (int64_t(1) << 31) || (!ring && c0 + S > ly->max_len) || ly->pos_offset < 0 ||
       c0 + S + ly->pos_offset >= (int64_t(1) << 31))
     return KVQ_EINVAL;
   const float *klut = ly->klut_score ? ly->klut_score : ly->klut;
@@ -435,13 +494,22 @@ static int chunk_attention_launch(const kvq_layer *ly, int Hq, int S, int64_t c0
   a.scale_log2e = (1.0f / sqrtf((float)chunk::kD)) * 1.4426950408889634f;
   a.rt_freq = rope ? rope->inv_freq : nullptr;
   a.rt_af = rope ? rope->attention_factor : 1.f;
+  if (ring) {
+    const int64_t C = ly->max_len, N = c0 + S;
+    a.wn_window = (int)window;                         // (<= max_len < 2^31: plan_window)
+    a.wn_cap = (int)C;
+    a.wn_res = (int)(N < C ? N : C);
+    a.wn_r = (int)((N - 1) % C);
+    a.wn_base = (int)((N - 1) / C * C);
+  }
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)((int64_t)(grouped ? ly->H : Hq * p.nqb) * p.nsplit)), block(chunk::kThreads);
   with_bits(bits, [&](auto B) {
-    with_int<0, 1, 2>(parent ? 2 : grouped ? 1 : 0, [&](auto V) {       // per-head, grouped, tree
+    with_int<0, 1, 2, 3, 4>(ring ? (grouped ? 4 : 3) : parent ? 2 : grouped ? 1 : 0, [&](auto V) {
       with_bool(rope != nullptr, [&](auto RT) {
-        constexpr int v = decltype(V)::value;
-        chunk::chunk_attn_kernel<decltype(B)::value, decltype(RT)::value, v >= 1, v == 2><<<grid, block, 0, st>>>(a);
+        constexpr int v = decltype(V)::value;          // per-head, grouped, tree, window per-head, window grouped
+        chunk::chunk_attn_kernel<decltype(B)::value, decltype(RT)::value, v == 1 || v == 2 || v == 4, v == 2, v >= 3>
+            <<<grid, block, 0, st>>>(a);
       });
     });
   });
@@ -516,6 +584,37 @@ int kvq_chunk_attention_tree_rope(const kvq_layer *ly, int Hq, int S, int64_t c0
   if (!parent) return KVQ_EINVAL;
   return chunk_attention_launch(ly, Hq, S, c0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
                                 workspace_bytes, rope, stream, true, parent);
+}
+
+size_t kvq_chunk_attention_window_workspace_bytes(int Hq, int Hkv, int S, int64_t n0, int64_t window, int64_t max_len) {
+  chunk::Plan p;
+  if (!chunk::plan_window(Hq, Hkv, S, n0, window, max_len, p, false)) return 0;
+  return p.o_bytes + p.ml_bytes;
+}
+
+int kvq_chunk_attention_window(const kvq_layer *ly, int Hq, int S, int64_t n0, int64_t window, const void *q,
+                               int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink, const uint16_t *v_sink,
+                               int n_sink, float *out, void *workspace, size_t workspace_bytes, const kvq_rope *rope,
+                               void *stream) {
+  if (window < 1) return KVQ_EINVAL;
+  return chunk_attention_launch(ly, Hq, S, n0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, rope, stream, false, nullptr, window);
+}
+
+size_t kvq_chunk_attention_window_grouped_workspace_bytes(int Hq, int Hkv, int S, int64_t n0, int64_t window,
+                                                          int64_t max_len) {
+  chunk::Plan p;
+  if (!chunk::plan_window(Hq, Hkv, S, n0, window, max_len, p, true)) return 0;
+  return p.o_bytes + p.ml_bytes;
+}
+
+int kvq_chunk_attention_window_grouped(const kvq_layer *ly, int Hq, int S, int64_t n0, int64_t window, const void *q,
+                                       int64_t q_stride_h, int64_t q_stride_s, const uint16_t *k_sink,
+                                       const uint16_t *v_sink, int n_sink, float *out, void *workspace,
+                                       size_t workspace_bytes, const kvq_rope *rope, void *stream) {
+  if (window < 1) return KVQ_EINVAL;
+  return chunk_attention_launch(ly, Hq, S, n0, q, q_stride_h, q_stride_s, k_sink, v_sink, n_sink, out, workspace,
+                                workspace_bytes, rope, stream, true, nullptr, window);
 }
 
 }  // extern "C"

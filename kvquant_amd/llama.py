@@ -46,6 +46,7 @@ import torch.nn as nn
 
 from . import sharding
 from .attention import KVQuantAttention, gqa_groups
+from .cache import ring_truncate_ok
 from .rope import RopeSpec
 from .spec import MAX_DRAFT, accept_draft, accept_tree, cut_tree, ngram_draft, ngram_tree_draft
 
@@ -99,11 +100,36 @@ def rope_spec_of(model):
     return spec
 
 
-def patch_llama(model, sparsity_threshold=0.99, compact=False):
-    """give every decoder layer's self_attn the compressed KV path.  `model`: LlamaForCausalLM / LlamaModel whose
-    config carries the KVQuant fields (kvquant_config).  Caches are created on each layer's current device.
+def layer_windows(cfg, n_layers, sliding_window=None):
+    """the sliding window of every decoder layer, [W or None] * n_layers.  sliding_window None: what the config says --
+    config.sliding_window, ignored where config.use_sliding_window is False, and only for the layers config.layer_types
+    marks "sliding_attention" where that list exists; 0: full attention everywhere; W >= 1: that window (still only on the
+    layers layer_types marks, where present)."""
+    if sliding_window is None:
+        W = getattr(cfg, "sliding_window", None)
+        if getattr(cfg, "use_sliding_window", True) is False:
+            W = None
+    else:
+        W = int(sliding_window)
+        if W < 0:
+            raise ValueError("sliding_window must be None (read the config), 0 (full attention) or >= 1")
+    if not W:
+        return [None] * n_layers
+    types_ = getattr(cfg, "layer_types", None)
+    if types_:
+        return [int(W) if (i < len(types_) and types_[i] == "sliding_attention") else None for i in range(n_layers)]
+    return [int(W)] * n_layers
+
+
+def patch_llama(model, sparsity_threshold=0.99, compact=False, sliding_window=None, window_slack=256):
+    """give every decoder layer's self_attn the compressed KV path.  `model`: LlamaForCausalLM / LlamaModel (or a
+    MistralForCausalLM: the same module structure) whose config carries the KVQuant fields (kvquant_config).  Caches are
+    created on each layer's current device.
     compact=True: the opt-in 4-byte outlier entries (fp16 residual + channel; kvquant_amd.cache) -- the
-    GPU-resident paths only, lossy against the reference format by the fp16 rounding of the residuals."""
+    GPU-resident paths only, lossy against the reference format by the fp16 rounding of the residuals.
+    sliding_window (layer_windows): None reads config.sliding_window, 0 forces full attention, W >= 1 sets the window.  A
+    windowed layer keeps RING caches of window_capacity(W, window_slack) columns (KVQuantAttention(sliding_window=W)):
+    config.maxseqlen does not bound its stream."""
     cfg = model.config
     kvquant_config(cfg)
     n_kv = kv_heads_of(cfg)
@@ -114,7 +140,8 @@ def patch_llama(model, sparsity_threshold=0.99, compact=False):
         theta = (getattr(cfg, "rope_parameters", None) or {}).get("rope_theta", 10000.0)
     base = model.model if hasattr(model, "model") else model
     rope = rope_spec_of(model)
-    for layer in base.layers:
+    windows = layer_windows(cfg, len(base.layers), sliding_window)
+    for layer, window in zip(base.layers, windows):
         attn = layer.self_attn
         dev = next(attn.parameters()).device
         core = KVQuantAttention(hidden_size=cfg.hidden_size, num_heads=cfg.num_attention_heads, abits=cfg.abits,
@@ -122,7 +149,7 @@ def patch_llama(model, sparsity_threshold=0.99, compact=False):
                                 maxseqlen=cfg.maxseqlen, rope_theta=float(theta), sparsity_threshold=sparsity_threshold,
                                 device=dev, dtype=next(attn.parameters()).dtype, make_proj=False, compact=compact,
                                 num_key_value_heads=None if n_kv == cfg.num_attention_heads else n_kv,
-                                rope_scaling=rope)
+                                rope_scaling=rope, sliding_window=window, window_slack=window_slack)
         # plain attributes, like the reference's (ML:1440-1466): they do not follow module.to(); use set_devices
         object.__setattr__(attn, "kvq", core)
         object.__setattr__(attn, "kcache", core.kcache)
@@ -152,6 +179,11 @@ def rollback(model, n_tokens):
         if core.kcache.klen != core.vcache.vlen or not 0 <= n_tokens <= core.kcache.klen - core.first_few_fp16:
             raise ValueError("rollback(%d): a layer holds %d / %d tokens, %d of them fp16 sink tokens"
                              % (n_tokens, core.kcache.klen, core.vcache.vlen, core.first_few_fp16))
+        kc = core.kcache
+        if getattr(kc, "window", None) is not None and not ring_truncate_ok(
+                kc.klen - core.first_few_fp16, n_tokens, kc.window, kc.max_len, kc.high_water):
+            raise ValueError("rollback(%d): past the slack of a sliding-window layer's ring cache (%d columns, window %d)"
+                             % (n_tokens, kc.max_len, kc.window))
     for core in cores:
         core.rollback(n_tokens)
 
@@ -440,6 +472,8 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
     if int(draft_branches) > 1:
         for core in _cores(model):
             kc, vc = core.kcache, core.vcache
+            if getattr(core, "sliding_window", None) is not None:
+                raise ValueError("draft trees (draft_branches > 1) are not taken on sliding-window layers (ring caches)")
             dtype = next(model.parameters()).dtype
             if not (kc.include_sparse and vc.include_sparse) or kc.compact or vc.compact \
                     or getattr(kc, "use_orig_sparse", False) or dtype != torch.float16 or core.head_dim != 128:
@@ -487,6 +521,19 @@ def generate(model, input_ids, max_length=None, max_new_tokens=None, eos_token_i
     return seq
 
 
+def _draft_room(model):
+    """draft rows the caches take behind the next token: what is left of a linear cache; capacity - window on a ring
+    (the chunk then fits one piece and its rollback the slack)"""
+    room = 1 << 30
+    for core in _cores(model):
+        kc = core.kcache
+        if getattr(core, "sliding_window", None) is not None:
+            room = min(room, kc.max_len - kc.window)
+        else:
+            room = min(room, kc.max_len - (kc.klen - core.first_few_fp16) - 1)
+    return room
+
+
 def _generate_speculative(model, input_ids, max_length, eos_token_id, min_length, draft_len, drafter, stats):
     """the draft_len > 0 loop of generate(): invariant at the top of a round -- the caches hold every token of `seq` but
     the last, `feed` is that last token (first round: the prompt) followed by the draft"""
@@ -519,7 +566,7 @@ def _generate_speculative(model, input_ids, max_length, eos_token_id, min_length
             break
         # the next draft: never past max_length (the round adds len(draft) + 1 tokens at most) nor past the cache
         klen, sinks = core.kcache.klen, core.first_few_fp16
-        k = min(draft_len, max_length - seq.shape[1] - 1, core.kcache.max_len - (klen - sinks) - 1)
+        k = min(draft_len, max_length - seq.shape[1] - 1, _draft_room(model))
         draft = []
         if k > 0 and klen >= sinks:
             draft = [int(t) for t in drafter(seq[0], k)][:k]
@@ -608,6 +655,9 @@ def inference_main(argv=None):
                     help="(extra) with --draft-len: verify a TREE of the continuations of up to this many earlier "
                          "occurrences of the suffix n-gram per forward (1: a chain)")
     ap.add_argument("--ngram", type=int, default=3, help="(extra) longest n-gram the prompt-lookup drafter matches")
+    ap.add_argument("--sliding-window", type=int, default=None,
+                    help="(extra) sliding-window attention on ring caches: the window in tokens (default: the model "
+                         "config's sliding_window; 0: full attention)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("kvquant_amd.llama needs a GPU (no CPU fallback)")
@@ -638,7 +688,7 @@ def inference_main(argv=None):
         gen = torch.Generator(device=dev).manual_seed(args.seed)
     if args.abits != 16:
         set_devices(model)
-        patch_llama(model, sparsity_threshold=args.sparsity_threshold)
+        patch_llama(model, sparsity_threshold=args.sparsity_threshold, sliding_window=args.sliding_window)
         print("Load quantizers.")
         load_quantizers(model, args.quantizer_path, args.include_sparse, args.sparsity_threshold, args.norm)
         t1 = time.time()
@@ -692,6 +742,9 @@ def main(argv=None):
     ap.add_argument("--first_few_fp16", type=int, default=0, help="Store first few tokens separately in fp16")
     ap.add_argument("--norm", action="store_true", help="Whether to use q-norm.")
     ap.add_argument("--generate", type=int, default=0, help="(extra) greedy-generate this many tokens after the benchmark prompt")
+    ap.add_argument("--sliding-window", type=int, default=None,
+                    help="(extra) sliding-window attention on ring caches: the window in tokens (default: the model "
+                         "config's sliding_window; 0: full attention)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("kvquant_amd.llama needs a GPU (no CPU fallback)")
@@ -706,7 +759,7 @@ def main(argv=None):
                                 seqlen=model.seqlen, vocab_size=model.config.vocab_size)
     if args.abits != 16:
         set_devices(model)                       # (ML:2428-2453) before the caches exist: they are created where the layer lives
-        patch_llama(model, sparsity_threshold=args.sparsity_threshold)
+        patch_llama(model, sparsity_threshold=args.sparsity_threshold, sliding_window=args.sliding_window)
         print("Load quantizers.")
         load_quantizers(model, args.quantizer_path, args.include_sparse, args.sparsity_threshold, args.norm)
     else:

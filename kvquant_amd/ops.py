@@ -840,16 +840,22 @@ def chunk_attention_route(Hq, Hkv, S):
     return "heads"
 
 
-def _chunk_call(what, name, layer, Hq, c0, q, out, k_sink, v_sink, rope, parent=None):
-    """the q / sink checks, output, workspace and call that chunk_attention and chunk_attention_tree share: runs the
-    library's <name>_rope (workspace from <name>_workspace_bytes; name None: by chunk_attention_route); parent: the tree
-    entry's extra argument"""
+def _chunk_args(q, Hq, k_sink, v_sink):
+    """the q / sink argument checks of the chunk entries"""
     if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float16 and q.dim() == 3 and q.stride(2) == 1):
         raise ValueError("q: expected an fp16 GPU tensor [Hq, S, 128] with a contiguous last dimension")
     if q.shape[0] != Hq or q.shape[2] != 128:
         raise ValueError("q: expected [%d, S, 128], got %s" % (Hq, tuple(q.shape)))
     if (k_sink is None) != (v_sink is None):
         raise ValueError("k_sink and v_sink come together")
+
+
+def _chunk_call(what, name, layer, Hq, c0, q, out, k_sink, v_sink, rope, parent=None, window=None):
+    """the q / sink checks, output, workspace and call that chunk_attention, chunk_attention_tree and
+    chunk_attention_window share: runs the library's <name>_rope (workspace from <name>_workspace_bytes; name None: by
+    chunk_attention_route); parent: the tree entry's extra argument; window: the window entries' (whose names carry no
+    _rope, whose c0 is n0 and whose workspace function also takes the ring's capacity)"""
+    _chunk_args(q, Hq, k_sink, v_sink)
     S = int(q.shape[1])
     extra = ()
     if parent is not None:
@@ -862,15 +868,19 @@ def _chunk_call(what, name, layer, Hq, c0, q, out, k_sink, v_sink, rope, parent=
     with _Dev(out):
         if name is None:
             name = "kvq_chunk_attention_grouped" if chunk_attention_route(Hq, layer.H, S) == "grouped" else "kvq_chunk_attention"
-        nbytes = getattr(_L(), name + "_workspace_bytes")(int(Hq), layer.H, S, int(c0))
+        at = (int(c0),) if window is None else (int(c0), int(window))
+        nbytes = getattr(_L(), name + "_workspace_bytes")(int(Hq), layer.H, S, *at,
+                                                          *(() if window is None else (int(layer.max_len),)))
         if nbytes == 0:
-            raise ValueError("%s: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d)" % (what, Hq, layer.H, S, c0))
+            raise ValueError("%s: unsupported shape (Hq=%d, Hkv=%d, S=%d, c0=%d%s)" % (
+                what, Hq, layer.H, S, c0, "" if window is None else ", window=%d on %d columns" % (window, layer.max_len)))
         base, usable, ws = _aligned_workspace(out.device, nbytes, "chunk")
-        _lib.check(getattr(_L(), name + "_rope")(
-            ctypes.byref(layer), int(Hq), S, int(c0), q.data_ptr(), q.stride(0), q.stride(1),
+        fn = name + "_rope" if window is None else name
+        _lib.check(getattr(_L(), fn)(
+            ctypes.byref(layer), int(Hq), S, *at, q.data_ptr(), q.stride(0), q.stride(1),
             None if k_sink is None else _chk(k_sink, torch.float16, "k_sink"),
             None if v_sink is None else _chk(v_sink, torch.float16, "v_sink"), n_sink, _f(out, "out"),
-            base, usable, *extra, _rope(rope, out.device), _stream()), name + "_rope")
+            base, usable, *extra, _rope(rope, out.device), _stream()), fn)
     return out
 
 
@@ -881,6 +891,44 @@ def chunk_attention(layer, Hq, c0, q, out=None, k_sink=None, v_sink=None, rope=N
     [Hkv, 128, n_sink] (post-RoPE) / v_sink fp16 [Hkv, n_sink, 128], or None.  Returns out f32 [S, Hq, 128].
     Shapes chunk_attention_route() sends to "grouped" run kvq_chunk_attention_grouped (same arguments and semantics)."""
     return _chunk_call("chunk_attention", None, layer, Hq, c0, q, out, k_sink, v_sink, rope)
+
+
+def chunk_attention_window(layer, Hq, n0, window, q, out=None, k_sink=None, v_sink=None, rope=None, grouped=None):
+    """kvq_chunk_attention_window[_grouped]: sliding-window attention of a chunk over a RING of C = layer.max_len
+    compressed columns (token n in column n mod C; the chunk's tokens n0 .. n0+S-1 already packed).  Query i of q (fp16
+    [Hq, S, 128] view, RoPE'd at pos_offset + n0 + i) sees the fp16 sink tokens and the `window` newest tokens up to its
+    own, each column rotated at the position of the token it holds.  grouped: True / False picks the geometry, None
+    leaves it to chunk_attention_route().  ValueError for what the library's workspace function refuses (window < 1,
+    window + S - 1 > C, C % 64 != 0, n0 < 0 and every shape chunk_attention refuses).  Returns out f32 [S, Hq, 128]."""
+    if grouped is None:
+        grouped = chunk_attention_route(Hq, layer.H, int(q.shape[1]) if torch.is_tensor(q) and q.dim() == 3 else 0) == "grouped"
+    name = "kvq_chunk_attention_window_grouped" if grouped else "kvq_chunk_attention_window"
+    return _chunk_call("chunk_attention_window", name, layer, Hq, n0, q, out, k_sink, v_sink, rope, window=int(window))
+
+
+def chunk_attention_window_check(layer, Hq, n0, window, q, k_sink=None, v_sink=None, rope=None, grouped=None):
+    """ValueError for every call chunk_attention_window(...) would refuse, without a launch: the argument checks of the
+    binding and the host checks of kvq_chunk_attention_window (shape, window, ring, position overflow, q strides and
+    alignment, sinks).  For callers that must know before they pack the chunk (cache.chunk_kv).  Returns the geometry
+    (`grouped`) the call will run, to be handed on to it."""
+    _chunk_args(q, Hq, k_sink, v_sink)
+    S = int(q.shape[1])
+    for t, name in ((k_sink, "k_sink"), (v_sink, "v_sink")):
+        if t is not None:
+            _chk(t, torch.float16, name)
+    _rope(rope, q.device)
+    if grouped is None:
+        grouped = chunk_attention_route(Hq, layer.H, S) == "grouped"
+    ws = getattr(_L(), "kvq_chunk_attention_window_grouped_workspace_bytes" if grouped else
+                 "kvq_chunk_attention_window_workspace_bytes")
+    n_sink = 0 if k_sink is None else int(k_sink.shape[2])
+    if ws(int(Hq), layer.H, S, int(n0), int(window), int(layer.max_len)) == 0 or \
+            layer.pos_offset < 0 or int(n0) + S + layer.pos_offset >= 2 ** 31 or not 0 <= n_sink <= 64 or \
+            (q.stride(0) | q.stride(1)) % 8 or q.data_ptr() % 16:
+        raise ValueError("chunk_attention_window: unsupported call (Hq=%d, Hkv=%d, S=%d, n0=%d, window=%d on %d columns, "
+                         "position offset %d, %d sink tokens, q strides %s)"
+                         % (Hq, layer.H, S, n0, window, layer.max_len, layer.pos_offset, n_sink, tuple(q.stride())))
+    return grouped
 
 
 # ---- draft trees: tree mask + per-node positions on the grouped kernel, and the accepted path -------------------------
